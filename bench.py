@@ -4,7 +4,7 @@
 1100 veh/h/lane), weak-scaled env-parallel over N GPUs (one process per GPU, no data-path collective;
 one RCCL all-gather of the metrics vector after the timed region).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 without an outer launcher: bench.py starts `python -m torch.distributed.run --nproc-per-node N bench.py ...`
 as a child process (before anything touches the GPU) and forwards rank 0's JSON line and the children's exit code.
@@ -15,11 +15,20 @@ says; then W un-timed warm-up steps, then EXACTLY K timed steps between barrier 
 one fused tick (all step() calls + scene_update() + delete_vehicle()) of every env of the rank.  Inputs (arrival
 streams, action pool) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-After the timed region (outside it) the line certifies itself: 8 of the envs this rank timed are replayed from reset by
-the CPU oracle and compared (final state + the last tick's outputs): "verified": true / false, exit code != 0 on false.
-`roofline` carries three HBM fractions (bytes the measured mode must move / SURVEY 8d's nominal 380 B / PMC counter bytes)
-and `binding`, the roofline that actually limits the kernel (vector-instruction issue, from the SQ counter passes of the
-same build); `retained_outputs` is the same workload with every tick's outputs kept (second timed region).
+--dump-outputs DIR: right after the timed region, rank 0 writes the outputs of the last timed tick (what the caller of the
+timed path receives: obs_post, reward, flags, ... as float64, float32 rows stay float32) to DIR/<name>.npy, for a fixed,
+seeded sample of the envs when all of them would exceed 60 MB, so that the files stay under 64 MB (DIR/env_index.npy lists
+the envs written).  The inputs
+depend on the arguments only, so two builds run with the same arguments can be compared output for output.
+
+A plain run does only what the headline figure needs.  --full adds everything else, all outside the timed region: the
+line certifies itself (8 of the envs this rank timed are replayed from reset by the CPU oracle and compared, final state
++ the last tick's outputs: "verified": true / false, exit code != 0 on false); `retained_outputs` is the same workload with
+every tick's outputs kept (second timed region), `tape_*`, `closed_loop`, `cap64*`, `config2_rate_128slots` and, with
+several ranks, `config4` time further configurations; `roofline.peak_measured` times a device copy and `cpu_baseline`
+the CPU oracle.  `roofline` carries three HBM fractions (bytes the measured mode must move / SURVEY 8d's nominal 380 B /
+PMC counter bytes) and `binding`, the roofline that actually limits the kernel (vector-instruction issue, from the SQ
+counter passes of the same build).
 """
 import argparse
 import hashlib
@@ -390,6 +399,7 @@ def run_companion(torch, dev, kind, K, W, rank, n_envs, verify=True, vseed=0):
     obs_dtype = torch.float32 if closed else torch.float64
     outputs = ("obs_post", "reward", "flags", "nbr", "new_slot", "env_out")
     n_sub, chunk, pers = launch_shape(cap, K, 12, closed, table=not closed, n_envs=n_envs)
+    pers = persistent_call(pers, chunk, K)
     if n_sub == 1:
         env = pve_mcc_amd.BatchedIntersections(n_envs, cap, arr, device=dev, outputs=outputs, obs_dtype=obs_dtype)
     else:
@@ -437,7 +447,7 @@ def run_companion(torch, dev, kind, K, W, rank, n_envs, verify=True, vseed=0):
                                     skip_overflowed=on_spec, seed=vseed)
     b_nom = B_ALG_OBS_F32 if closed else B_ALG_FP64
     # ticks per launch / per queue item: the state crosses HBM once per that many ticks
-    tpl = (K / float(persistent_items(K, chunk))) if pers else (chunk if chunk > 0 else K)
+    tpl = (K / float(persistent_items(K, chunk))) if pers else (min(chunk, K) if chunk > 0 else K)
     b_alg = b_nom - (B_STATE_IN + B_STATE_OUT) * (1.0 - 1.0 / tpl)
     res = {"what": ("BASELINE config 5: %d x %d, 1000 veh/h/lane, MADDPG actor (pretrained 66.cptk weights) inside the resident "
                     "kernel, float32 rows, pve_step_many(PVE_SRC_ACTOR)" if closed else
@@ -452,7 +462,7 @@ def run_companion(torch, dev, kind, K, W, rank, n_envs, verify=True, vseed=0):
                      "BASELINE config 2: %d x %d, BASELINE.md 3's tape a = float32(sin(0.37 id + 0.05 tick)) by vehicle id, 350 veh/h/lane "
                      "(BASELINE.md's 500 overflows 64 slots in 4096 envs: the `cap64_on_spec` leg)")) % (n_envs, cap),
            "ms_per_step": dt / K * 1e3, "value": float(cap) * n_envs * K / dt, "unit": "env-steps/s", "steps": K, "warmup": W,
-           "prefill_ticks": prefill, "ticks_per_launch": K if (pers or chunk == 0) else chunk, "ticks_per_item": tpl,
+           "prefill_ticks": prefill, "ticks_per_launch": K if (pers or chunk == 0) else min(chunk, K), "ticks_per_item": tpl,
            "sub_batches": n_sub, "launch": "persistent work queue" if pers else "one launch per chunk and sub-batch",
            "verified": ver["verified"], "envs_compared": ver.get("envs_compared", len(ver.get("envs", []))),
            "envs_skipped_overflowed": len(ver.get("envs_skipped_overflowed", [])), "verification": ver,
@@ -577,6 +587,12 @@ def persistent_items(K, T, lib=None):
     return len(item_schedule(K, T, lib))
 
 
+def persistent_call(pers, chunk, K):
+    """Whether a call of K ticks asked for as `pers` with items of `chunk` ticks IS one persistent launch: pve_step_many
+    runs the queue for 0 < chunk < K only (one chunked launch otherwise), and only then has an item schedule."""
+    return bool(pers) and 0 < chunk < K
+
+
 def launch_shape(cap, K, lane_num, actor, table=False, trajectory=False, n_envs=4096):
     """Default launch shape of a roll-out of K ticks: (sub-batches, ticks per launch or queue item, persistent).
     Measured on MI355X with 4096 envs (tools/ab_launch_shapes.py, same process, medians):
@@ -642,6 +658,25 @@ def measured_copy_peak(torch, dev):
     return 2.0 * n / (best * 1e-3) / 1e9
 
 
+DUMP_BYTES, DUMP_SEED = 60 * 10 ** 6, 20250213    # --dump-outputs: at most 60 MB of arrays (< 64 MB with the .npy headers)
+
+
+def dump_outputs(outs, n_envs, path):
+    """--dump-outputs: outs = {name: tensor [n_envs, ...]} of the last timed tick -> path/<name>.npy, float64 (float32 stays
+    float32), rows of a fixed, seeded sample of the envs if all of them would exceed DUMP_BYTES; path/env_index.npy lists
+    the envs written.  -> number of envs written."""
+    arrs = {n: t.detach().cpu().numpy() for n, t in outs.items()}
+    arrs = {n: a if a.dtype == np.float32 else a.astype(np.float64) for n, a in arrs.items()}
+    per_env = 8 + sum(a[0].nbytes for a in arrs.values()) if n_envs else 8
+    n_keep = min(n_envs, DUMP_BYTES // per_env)
+    rows = np.arange(n_envs) if n_keep == n_envs else np.sort(np.random.default_rng(DUMP_SEED).choice(n_envs, n_keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for n, a in arrs.items():
+        np.save(os.path.join(path, n + ".npy"), np.ascontiguousarray(a[rows]))
+    np.save(os.path.join(path, "env_index.npy"), rows.astype(np.float64))
+    return int(n_keep)
+
+
 def main(argv=None, env_factory=None):
     """env_factory: tests inject a factory (device, backend, builder) to exercise the rank plumbing and the
     JSON contract without a GPU; the product run never passes it."""
@@ -698,6 +733,11 @@ def main(argv=None, env_factory=None):
     ap.add_argument("--actor", action="store_true",
                     help="BASELINE config 5: close the loop on the device instead of the action pool -- rollout mode: the actor "
                          "runs inside the resident kernel (pve_step_many(PVE_SRC_ACTOR)); step mode: actor launch + tick launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed tick's outputs to DIR/<name>.npy (a fixed sample of the envs above 60 MB: under 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle replay of the timed envs, the companion regions and configurations, "
+                         "the device copy peak and the CPU baseline (a plain run times the headline only)")
     args = ap.parse_args(argv)
     if args.actor and not args.obs_f64:
         args.obs_f32 = True
@@ -754,7 +794,8 @@ def main(argv=None, env_factory=None):
     id_sin = (args.tape == "id-sin") and lane_num == 12 and not args.actor and not emu
     table_np = None
     if id_sin:
-        table_np = id_sin_table(prefill_cap + W + 4 * K + 256)     # (headline + the retained-outputs companion behind it)
+        # (headline + with --full the retained-outputs companion behind it; rows past the last tick are never read)
+        table_np = id_sin_table(prefill_cap + W + (4 * K if args.full else K) + 256)
     outputs = tuple(x for x in args.outputs.split(",") if x)
     # launch shape: launch_shape()'s measured default unless --pipeline / --chunk / --persistent say otherwise
     rollout_like = (args.mode or ("rollout" if not emu else "step")) == "rollout"
@@ -768,6 +809,7 @@ def main(argv=None, env_factory=None):
         args.pipeline = 1 if pers else (d_sub if args.persistent is None else 2)
     if args.chunk is None:
         args.chunk = d_chunk if (pers == d_pers and args.pipeline == d_sub) else ((25 if K >= 100 else 5) if (cap == 128 or pers) else 0)
+    pers = persistent_call(pers, args.chunk, K)          # (K <= chunk: one chunked launch, what pve_step_many runs then)
     n_sub = 1 if pers else max(1, min(args.pipeline, n_envs))
     obs_dtype = torch.float32 if args.obs_f32 else torch.float64
     if emu:
@@ -928,17 +970,31 @@ def main(argv=None, env_factory=None):
     rank_ms = [float(x) for x in per_rank[:, NM]]
     rank_env0 = [int(x) for x in per_rank[:, NM + 1]]
     rank_ticks = [float(x) / n_envs for x in per_rank[:, pve_mcc_amd._capi.METRIC_NAMES.index("ticks")]]
-
-    # ---- self-check, outside the timed region: the envs that were timed against the CPU oracle
-    verify = dict(verified=None, reason="skipped (--no-verify)")
     subs = getattr(env, "subs", None)
+
+    # ---- what the timed path handed its caller in its last tick, before anything else runs on these envs
+    dumped_envs, tick_dumped = None, tick[0]
+    if args.dump_outputs and rank == 0:
+        parts = subs if subs is not None else [env]
+        if traj_on:                                       # the last tick's block of the last call's trajectory buffer
+            tr = ring[ring_pos[1]]
+            per_sub = [{n: t[ring_pos[2] - 1] for n, t in (tr[k] if subs is not None else tr).items()} for k in range(len(parts))]
+        else:
+            per_sub = [p.outputs() for p in parts]
+        sync()
+        dumped_envs = dump_outputs({n: torch.cat([o[n] for o in per_sub]) for n in per_sub[0]}, n_envs, args.dump_outputs)
+
+    # ---- self-check (--full), outside the timed region: the envs that were timed against the CPU oracle
+    verify = dict(verified=None, reason="skipped (--no-verify)")
 
     def locate(e):
         if subs is None:
             return env, e
         k, le = env.sub_of(e)
         return subs[k], le
-    if args.actor and not args.no_verify and not emu:
+    if not args.full:
+        verify = dict(verified=None, reason="not run: the replay of the timed envs is part of --full")
+    elif args.actor and not args.no_verify and not emu:
         sync()
         verify = verify_closed_loop(torch, dev, locate, arr, tick[0], cap, obs_dtype, actor_weights(), lane_num=lane_num, choice=choice, seed=vseed)
     elif args.actor:
@@ -962,7 +1018,7 @@ def main(argv=None, env_factory=None):
     # ticks with every tick's outputs RETAINED (trajectory roll-outs into a ring of two chunk buffers per sub-batch: what a
     # trainer consumes) are timed right behind it, outside the headline region
     companion = None
-    if mode == "rollout" and not traj_on and not args.actor and not emu and world == 1 and not args.no_companion:
+    if args.full and mode == "rollout" and not traj_on and not args.actor and not emu and world == 1 and not args.no_companion:
         # calls of `tl` ticks, each into one buffer of the ring (with the persistent launch: one launch per call, items of
         # args.chunk ticks, every tick writing its own block)
         tl = (min(K, 25) if pers else (args.chunk if args.chunk > 0 else 25))
@@ -993,7 +1049,8 @@ def main(argv=None, env_factory=None):
     # ---- the slot-indexed sin pool (the headline of rounds 1-4) beside BASELINE.md 3's id-indexed tape, or the other way round
     # with --tape pool: K more ticks of the same envs under the other tape, timed outside the headline (and verified) region
     tape_id_sin = tape_slot_pool = None
-    if mode == "rollout" and not traj_on and not args.actor and not emu and world == 1 and lane_num == 12 and not args.no_companion:
+    if args.full and mode == "rollout" and not traj_on and not args.actor and not emu and world == 1 and lane_num == 12 \
+            and not args.no_companion:
         if id_sin:
             env.set_action_pool(pool)
             other_src = "pool"
@@ -1018,7 +1075,7 @@ def main(argv=None, env_factory=None):
             tape_id_sin = comp
     # ---- BASELINE configs 5 and 2 beside the headline (config 3), each on envs of its own, timed outside the headline region
     closed_loop = cap64 = cap64_on_spec = config2_rate_128slots = None
-    if mode == "rollout" and not traj_on and not args.actor and not emu and world == 1 and lane_num == 12 \
+    if args.full and mode == "rollout" and not traj_on and not args.actor and not emu and world == 1 and lane_num == 12 \
             and cap == 128 and not args.no_companion and K > 0:
         del env
         torch.cuda.empty_cache()
@@ -1028,7 +1085,7 @@ def main(argv=None, env_factory=None):
         config2_rate_128slots = run_companion(torch, dev, "config2_rate_128slots", K, W, rank, n_envs, verify=not args.no_verify, vseed=vseed + 6)
     # ---- multi-rank runs carry BASELINE config 4 (64-slot intersections sharded over the ranks) beside the weak-scaled headline
     config4 = None
-    if world > 1 and lane_num == 12 and not args.no_companion and K > 0 and (mode == "rollout" or emu):
+    if args.full and world > 1 and lane_num == 12 and not args.no_companion and K > 0 and (mode == "rollout" or emu):
         del env
         config4 = run_config4(torch, dist, dev, K, W, rank, world, n_envs, env_factory=env_factory, verify=not args.no_verify, vseed=vseed + 5)
     ok_flag = 0.0 if (verify["verified"] is False or any(c and c.get("verified") is False for c in (closed_loop, cap64, cap64_on_spec, config2_rate_128slots, config4, companion))) else 1.0
@@ -1043,7 +1100,7 @@ def main(argv=None, env_factory=None):
         slot_steps = float(cap) * n_envs * K * world
         value = slot_steps / wall
         envs_per_launch = n_envs / float(n_sub)
-        tpl = (traj_len if traj_on else (args.chunk if args.chunk > 0 else K)) if mode == "rollout" else 1      # ticks per kernel launch
+        tpl = (traj_len if traj_on else (min(args.chunk, K) if args.chunk > 0 else K)) if mode == "rollout" else 1      # ticks per kernel launch
         if pers:
             tpl = K                                       # one launch for the whole call ...
         # ... whose items move an intersection's state across HBM once each
@@ -1073,7 +1130,7 @@ def main(argv=None, env_factory=None):
         tr, traffic_src = (None, None) if (emu or not steady) else pmc_traffic(int(envs_per_launch), cap, outputs, mode, tpl, other, pkey)
         traffic = tr["hbm_bytes_per_launch"] if tr else None
         counter_rate = (traffic / tpl * n_sub / (wall / K) / 1e9) if traffic else None
-        peak_meas = None if (emu or args.no_copy_peak) else measured_copy_peak(torch, dev)
+        peak_meas = None if (emu or args.no_copy_peak or not args.full) else measured_copy_peak(torch, dev)
         mean_alive = tot["alive_steps"] / (K * n_envs * world)
         # ---- what binds: VALU issue (SQ counters of this build), not bandwidth
         std_out = tuple(outputs) == ("obs_post", "reward", "flags", "nbr", "new_slot", "env_out")
@@ -1173,7 +1230,9 @@ def main(argv=None, env_factory=None):
         if peak_meas and achieved > peak_meas:
             line["roofline"]["note_above_copy_peak"] = ("algorithmic bytes exceed what a copy kernel moves in the same time: "
                                                         "empty slots are counted but not moved")
-        if not args.no_cpu_baseline and not args.actor and world == 1:      # reported at N=1 only
+        if dumped_envs is not None:
+            line["dumped_outputs"] = {"envs": dumped_envs, "of": n_envs, "tick": tick_dumped}
+        if args.full and not args.no_cpu_baseline and not args.actor and world == 1:      # reported at N=1 only
             line["cpu_baseline"] = cpu_baseline(arr, pool_np, cap, lane_num, choice, id_sin=id_sin)
         print(json.dumps(line), flush=True)
     if world > 1:

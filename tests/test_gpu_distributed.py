@@ -53,7 +53,7 @@ def test_bench_gpus_1_through_the_self_launcher_path():
     """`bench.py --gpus 1` under an outer torchrun-style environment (WORLD_SIZE=1): the nccl process group is not created
     for one rank, the line carries the steady-state protocol fields."""
     out = subprocess.check_output([sys.executable, "bench.py", "--envs", "256", "--steps", "20", "--warmup", "5",
-                                   "--no-cpu-baseline", "--no-copy-peak"], cwd=ROOT, text=True, timeout=900)
+                                   "--no-cpu-baseline", "--no-copy-peak", "--full"], cwd=ROOT, text=True, timeout=900)
     d = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
     assert d["population"] == "steady" and d["prefill_ticks"] >= 300 and d["mean_alive_per_env"] > 60
     r = d["roofline"]

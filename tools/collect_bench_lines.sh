@@ -7,8 +7,8 @@ R=${1:-r3}
 export TMPDIR=/tmp
 O=gpurun_out/$R
 mkdir -p $O
-B="python bench.py"
-NB="python bench.py --no-cpu-baseline --no-copy-peak --no-companion"
+B="python bench.py --full"
+NB="python bench.py --full --no-cpu-baseline --no-copy-peak --no-companion"
 timeout 400 $B 2>/dev/null | tail -1 > $O/bench_default.json
 timeout 400 $B --mode step 2>/dev/null | tail -1 > $O/bench_step.json
 timeout 400 $B --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_driver_like.json

@@ -7,8 +7,8 @@ R=${1:-r4}
 export TMPDIR=/tmp
 O=gpurun_out/$R
 mkdir -p $O
-B="python bench.py"
-NB="python bench.py --no-cpu-baseline --no-copy-peak --no-companion"
+B="python bench.py --full"
+NB="python bench.py --full --no-cpu-baseline --no-copy-peak --no-companion"
 run() { out=$1; shift; timeout 400 "$@" 2>/dev/null | tail -1 > $O/$out; }
 # ---- bench lines (default = the persistent launch for 12 lanes x 128 slots; --persistent 0 = two sub-batches, one launch per chunk)
 run bench_default.json $B

@@ -8,8 +8,8 @@ set -u
 export TMPDIR=/tmp
 R=r6; P=r06; O=gpurun_out/$R
 mkdir -p $O
-B="python bench.py"
-NB="python bench.py --no-cpu-baseline --no-copy-peak --no-companion"
+B="python bench.py --full"
+NB="python bench.py --full --no-cpu-baseline --no-copy-peak --no-companion"
 run() { out=$1; shift; timeout 400 "$@" 2>/dev/null | tail -1 > $O/$out; }
 bash tools/gpu.sh test > $O/gpu_suite.txt 2>&1
 lines() {

@@ -10,7 +10,7 @@
 set -u
 export TMPDIR=/tmp
 CSRC=pve-mcc_for_unsignalized_intersection_amd/csrc
-B="python bench.py --no-cpu-baseline --no-copy-peak --no-companion"
+B="python bench.py --full --no-cpu-baseline --no-copy-peak --no-companion"
 
 time_shape() {   # $1 = bench args, $2 = reps
   local args="$1" reps="${2:-3}" rep out rc

@@ -14,7 +14,7 @@ for grp in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_D
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_SALU" \
            "SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES SQ_WAIT_ANY SQ_WAVES"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --pmc $grp --kernel-trace -d "$OUT/p$i" -o p$i --output-format csv -- python3 "$REPO/bench.py" --steps 100 --warmup 300 --no-cpu-baseline --no-copy-peak "$@" > "$OUT/p$i.log" 2>&1
+  timeout 200 rocprofv3 --pmc $grp --kernel-trace -d "$OUT/p$i" -o p$i --output-format csv -- python3 "$REPO/bench.py" --full --steps 100 --warmup 300 --no-cpu-baseline --no-copy-peak "$@" > "$OUT/p$i.log" 2>&1
 done
 python3 - "$OUT" <<'PY' > "$REPO/gpurun_out/pmc_icache_$TAG.txt"
 import sys, glob, csv, collections

@@ -15,7 +15,7 @@ for grp in "TCP_PENDING_STALL_CYCLES TCP_TCP_TA_DATA_STALL_CYCLES TCP_TCR_TCP_ST
            "TCC_BUSY TCC_TAG_STALL TCC_WRITE TCC_WRITEBACK" \
            "SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_VMEM_RD SQ_VMEM_WR_TA_DATA_FIFO_FULL SQ_VMEM_TA_ADDR_FIFO_FULL SQ_VMEM_TA_CMD_FIFO_FULL"; do
   i=$((i+1))
-  timeout 150 rocprofv3 --pmc $grp --kernel-trace -d "$OUT/p$i" -o p$i --output-format csv -- python3 "$REPO/bench.py" --steps 20 --warmup 300 --no-cpu-baseline ${PMC_BENCH_ARGS:-} > "$OUT/p$i.log" 2>&1
+  timeout 150 rocprofv3 --pmc $grp --kernel-trace -d "$OUT/p$i" -o p$i --output-format csv -- python3 "$REPO/bench.py" --full --steps 20 --warmup 300 --no-cpu-baseline ${PMC_BENCH_ARGS:-} > "$OUT/p$i.log" 2>&1
 done
 python3 - "$OUT" <<'PY' > "$REPO/gpurun_out/pmc_mem_$TAG.txt"
 import sys, glob, csv, collections
