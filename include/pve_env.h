@@ -142,11 +142,13 @@ int pve_abi_version(void);
 const char *pve_last_error(void);
 void pve_default_config(pve_config *cfg);
 
-/* Bytes of device workspace a handle needs (persistent SoA vehicle state + env headers). */
+/* Bytes of device workspace a handle needs (persistent SoA vehicle state + env headers); 0 for a capacity the library has no
+ * kernels for.  pve_workspace_bytes(n, 256) > 0 is how a caller probes for the 256-slot capacity. */
 size_t pve_workspace_bytes(int n_envs, int capacity);
 
 /* Replaces `TrafficInteraction(arrive_time, dis_ctl, args, ...)` object creation (ref :21) for
- * n_envs independent intersections with `capacity` (64 or 128) vehicle slots each.
+ * n_envs independent intersections with `capacity` (64, 128 or 256) vehicle slots each.  256 slots: lane_num 12 on the fast
+ * path only; the 4- / 8-lane layouts and PVE_CFG_GENERAL_PATH at 256 return PVE_ERR_INVALID.
  * workspace: device buffer of pve_workspace_bytes() bytes, or NULL to let the library allocate. */
 int pve_create(const pve_config *cfg, int n_envs, int capacity, int device_id,
                void *workspace, void *stream, pve_handle *out);

@@ -31,6 +31,10 @@ def make_config(lib, **kw):
 class BatchedIntersections:
     """n_envs environments x `capacity` vehicle slots, state resident in HBM (struct of arrays).
 
+    capacity: 64, 128 or 256 slots per intersection.  256 needs lane_num = 12 on the fast path (not the 4- / 8-lane
+              layouts, not general_path); a full intersection defers its spawns (metrics()["overflow"]), so a dense
+              arrival stream or a slow policy wants 256.
+
     arrivals: float64 array/tensor [rows, lane_num] (shared by all envs) or [n_envs, rows, lane_num]; the
               reference's `arrive_time` matrix (main.py:388-389). Pad with +inf.
     outputs:  names of per-tick output buffers to allocate (see include/pve_env.h `pve_outputs`).
@@ -70,7 +74,7 @@ class BatchedIntersections:
         self.dir_num = _capi.DIR_NUM.get(self.lane_num, 12)
         nbytes = self.lib.pve_workspace_bytes(self.n_envs, self.capacity)
         if nbytes == 0:
-            raise PveError("invalid n_envs/capacity (capacity must be 64 or 128)")
+            raise PveError("invalid n_envs/capacity (capacity must be 64, 128 or 256; 256 needs lane_num 12)")
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         dev_index = self.device.index if self.device.index is not None else (
             torch.cuda.current_device() if self.device.type == "cuda" else 0)
@@ -500,6 +504,7 @@ class BatchedIntersections:
 
 class PipelinedIntersections:
     """`n_envs` environments as `n_sub` sub-batches, each a BatchedIntersections on its own HIP stream.
+    (capacity: 64, 128 or 256 slots, as BatchedIntersections; 256 with lane_num = 12 only.)
 
     The environments are independent, so the sub-batches never synchronise with each other: tick t+1 of one is in
     flight while tick t of another still runs.  One launch over all envs runs its workgroups in lock-step (every

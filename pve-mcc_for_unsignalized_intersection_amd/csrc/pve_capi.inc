@@ -21,6 +21,7 @@
 //     static int   pack_actor(const float *W, float *flat, unsigned char *packed, void *stream, std::string &err);   // pve_set_actor
 //     static int   launch_actor(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
 //                               double *actions, int n_envs, int cap, void *stream, std::string &err);
+//     static constexpr int max_capacity = 256;   // optional: the largest capacity it runs (default 128, see backend_max_capacity)
 //   };
 //
 // pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
@@ -128,6 +129,15 @@ static void item_schedule(int K, int T, RolloutArgs &R)
     R.n_taper = n_taper;
 }
 
+// The largest capacity the backend has kernels for: Backend::max_capacity when it declares one, else 128.  256 slots exist for
+// the 12-lane fast path only (k_tick<256> / k_rollout<256, ..>); the 4- / 8-lane layouts and the general path stop at 128.
+template <class B, class = void> struct backend_max_capacity { static constexpr int value = 128; };
+template <class B> struct backend_max_capacity<B, decltype((void)B::max_capacity)> { static constexpr int value = B::max_capacity; };
+static bool capacity_known(int capacity)
+{
+    return capacity == 64 || capacity == 128 || (capacity == 256 && backend_max_capacity<Backend>::value >= 256);
+}
+
 extern "C" {
 
 int pve_abi_version(void) { return PVE_ABI_VERSION; }
@@ -143,7 +153,7 @@ void pve_default_config(pve_config *cfg)
 
 size_t pve_workspace_bytes(int n_envs, int capacity)
 {
-    if (n_envs <= 0 || (capacity != 64 && capacity != 128)) return 0;
+    if (n_envs <= 0 || !capacity_known(capacity)) return 0;
     return make_layout(n_envs, capacity).total;
 }
 
@@ -154,8 +164,12 @@ int pve_create(const pve_config *cfg, int n_envs, int capacity, int device_id, v
     if (cfg->lane_num != 12 && cfg->lane_num != 8 && cfg->lane_num != 4)
         return fail(PVE_ERR_INVALID, "pve_create: lane_num must be 12, 8 or 4 (the 3-lane branch is broken upstream)");
     if (n_envs <= 0) return fail(PVE_ERR_INVALID, "pve_create: n_envs must be > 0");
-    if (capacity != 64 && capacity != 128)
-        return fail(PVE_ERR_INVALID, "pve_create: capacity must be 64 or 128");
+    if (!capacity_known(capacity))
+        return fail(PVE_ERR_INVALID, backend_max_capacity<Backend>::value >= 256 ? "pve_create: capacity must be 64, 128 or 256"
+                                                                                  : "pve_create: capacity must be 64 or 128");
+    if (capacity == 256 && (cfg->lane_num != 12 || (cfg->flags & PVE_CFG_GENERAL_PATH)))
+        return fail(PVE_ERR_INVALID, "pve_create: capacity 256 needs lane_num 12 on the fast path (not the 4- / 8-lane layouts, "
+                                     "not PVE_CFG_GENERAL_PATH)");
     if (!(cfg->deltaT > 0) || !(cfg->am < 0) || !(cfg->aM > 0) || !(cfg->vM >= cfg->vm))
         return fail(PVE_ERR_INVALID, "pve_create: inconsistent limits (deltaT>0, am<0<aM, vM>=vm required)");
     if (!(fabs(cfg->am) >= 1e-6 && fabs(cfg->am) <= 1e6))
@@ -555,8 +569,9 @@ int pve_read_vehicles(pve_handle h, int env, pve_vehicle *out, int max_n, int *n
     const int m = n < max_n ? n : max_n;
     const int cap = h->cap;
     DevScope dev_scope(h->device);
-    double f[NF64][128];
-    int32_t iv[NI32][128];
+    static_assert(backend_max_capacity<Backend>::value <= 256, "pve_read_vehicles: the slot rows below hold 256 slots");
+    double f[NF64][256];
+    int32_t iv[NI32][256];
     if (h->n_envs == 1) {
         // single-env handles (the drop-in compatibility class): the whole workspace is ~11 KB, one copy
         std::string buf(h->L.total, '\0');

@@ -54,8 +54,10 @@ __device__ __forceinline__ void lds_barrier() { __syncthreads(); }
 // CAP = 128: 5 waves per SIMD (<= 96 VGPR) + the 15.1 KB LDS block = 10 workgroups of 128 threads per CU instead of 8: with
 // the sub-batches pipelined on several streams the tick scales almost linearly with the resident workgroups.
 // CAP = 64: one wave per workgroup, LDS (10 KB) admits 16 workgroups per CU = 4 waves per SIMD (<= 128 VGPR).
+// CAP = 256: four waves per workgroup and a ~32 KB block: LDS admits 5 workgroups per CU = 5 waves per SIMD; held to 4 waves per
+// SIMD (<= 128 VGPR, the budget of the 128-slot register build) so that the wider masks do not spill.
 template <int CAP>
-__global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(CAP == 64 ? 4 : 5, CAP == 64 ? 4 : 5))) void k_tick(const Const c_arg, const Params P_arg)
+__global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(CAP == 128 ? 5 : 4, CAP == 128 ? 5 : 4))) void k_tick(const Const c_arg, const Params P_arg)
 {
     KernargPtr ka0_ = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
     const PVE_AS4 Const &c = *(const PVE_AS4 Const *)ka0_;
@@ -117,9 +119,11 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(CAP == 64 ?
     if (P.out.state_pre) {            // uniform branch: optional training output
         __threadfence_block();
         __syncthreads();
-        T::ph_state_publish(P.out, t, sh, r);
-        __syncthreads();
-        T::ph_state_coop(P, P.out, env, t, sh);
+        if constexpr (CAP <= 128) {
+            T::ph_state_publish(P.out, t, sh, r);
+            __syncthreads();
+            T::ph_state_coop(P, P.out, env, t, sh);
+        } else T::ph_state(P, env, t, sh, r);        // (256 slots: the byte descriptors cannot name slots >= 128)
         PVE_PHASE_MARK(10)
     }
     if (P.phase_cycles && (t & 63) == 0) {
@@ -134,22 +138,22 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(CAP == 64 ?
 // chain is the workgroup's critical path -- so the work is split by TILE, not by owner: tile i = dense threads 32 i .. 32 i
 // + 31 goes to wave i % (CAP / 64).  A tile's rows are the float32 images of what FIN stored to obs_post a moment ago (same
 // CU: L1 / L2 hot, ordered by barrier A), addressed through the post-compaction slots the dense threads left in `adsts`
-// (255 = the vehicle is gone); lane (j, hf) fetches the half row it contracts.  act[slot] receives the action of every
+// (SLOT_NONE<CAP> = the vehicle is gone); lane (j, hf) fetches the half row it contracts.  act[slot] receives the action of every
 // controlled vehicle that keeps a slot.  The launch's first tick uses the same routine on the rows in HBM.
 template <int CAP>
-__device__ __forceinline__ void rollout_actor(const unsigned char *packed, const float *aprm, double *act, const uint8_t *adsts,
+__device__ __forceinline__ void rollout_actor(const unsigned char *packed, const float *aprm, double *act, const slot_t<CAP> *adsts,
                                               int n_ctl, const void *rows, bool obs_f32, size_t base, int t)
 {
     const pve_v8h *A1 = (const pve_v8h *)(packed + AP_A1), *A2 = (const pve_v8h *)(packed + AP_A2);
     const int lane = t & 63, hf = lane >> 5, j = lane & 31;
     for (int tile = t >> 6; 32 * tile < n_ctl; tile += CAP / 64) {          // (uniform per wave)
         const int slot = adsts[32 * tile + j];
-        const int srow = slot == 255 ? 0 : slot;
+        const int srow = slot == SLOT_NONE<CAP> ? 0 : slot;
         float x[16];
         if (obs_f32) actor_fetch_env((const float *)rows + base * OBSW, srow, hf, x);
         else actor_fetch_env((const double *)rows + base * OBSW, srow, hf, x);
         const float a = actor_tile32(A1, A2, aprm, x, lane);
-        if (lane < 32 && slot != 255) act[slot] = (double)a;
+        if (lane < 32 && slot != SLOT_NONE<CAP>) act[slot] = (double)a;
     }
 }
 
@@ -320,7 +324,7 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     typedef Shared<CAP, (CAP == 128 && WPE == 4), (WPE == 5)> ShT;
     __shared__ ShT sh;
     __shared__ __attribute__((aligned(64))) float aprm[ACT ? PV_TOTAL : 1];
-    __shared__ uint8_t adsts[ACT ? CAP : 1];         // post-compaction slot of every dense thread's vehicle (255: gone)
+    __shared__ slot_t<CAP> adsts[ACT ? CAP : 1];     // post-compaction slot of every dense thread's vehicle (SLOT_NONE: gone)
     __shared__ int q_word[4];                       // PERS: item (env, chunk) of the workgroup + the dequeue state of lane 0
     int adst = -1;
     int t0_ = threadIdx.x;
@@ -381,9 +385,9 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             const int mt = P.i32[I_META][(size_t)env0_ * CAP + t0_];
             const bool cc = (mt & (M_ALIVE | M_CONTROL)) == (M_ALIVE | M_CONTROL);
             vote<CAP / 64>(sh.m_ctl, t0_, cc);
-            adsts[t0_] = 255;                            // (entries beyond the controlled count: no vehicle)
+            adsts[t0_] = (slot_t<CAP>)SLOT_NONE<CAP>;  // (entries beyond the controlled count: no vehicle)
             lds_barrier();
-            if (cc) adsts[mask_rank<CAP / 64>(sh.m_ctl, t0_)] = (uint8_t)t0_;
+            if (cc) adsts[mask_rank<CAP / 64>(sh.m_ctl, t0_)] = (slot_t<CAP>)t0_;
             const int nc = mask_count<CAP / 64>(sh.m_ctl);
             lds_barrier();                               // parameters staged, list complete
             rollout_actor<CAP>(R.actor_packed, aprm, sh.act_next, adsts, nc, R.actor_obs, P.obs_f32 != 0, (size_t)env0_ * CAP, t0_);
@@ -525,7 +529,7 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         if constexpr (ACT) {
             adst = -1;
             T::template ph_final<true>(c, P, O, env, t, sh, r, fc, true, &adst);
-            adsts[t] = (uint8_t)(adst < 0 ? 255 : adst);  // (dense thread t; threads >= n_ctl: 255)
+            adsts[t] = (slot_t<CAP>)(adst < 0 ? SLOT_NONE<CAP> : adst);  // (dense thread t; threads >= n_ctl: SLOT_NONE)
         } else T::template ph_final<true, !TRAIN>(c, P, O, env, t, sh, r, fc, k + 1 == n_ticks || (TRAIN && O.state_pre != nullptr));
         PVE_PHASE_MARK(9)
         if constexpr (IDT) {
@@ -544,9 +548,11 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             //  ANOTHER workgroup's item stored -- block k - 1 of the trajectory --: coherent loads)
             if constexpr (TRAIN) {
                 if (O.state_pre) {                       // (uniform) the 7 x 28 states: descriptors, barrier, cooperative write
-                    T::ph_state_publish(O, t, sh, r);
-                    lds_barrier();
-                    T::template ph_state_coop<PERS>(P, O, env, t, sh);
+                    if constexpr (CAP <= 128) {
+                        T::ph_state_publish(O, t, sh, r);
+                        lds_barrier();
+                        T::template ph_state_coop<PERS>(P, O, env, t, sh);
+                    } else T::template ph_state<PERS>(P, O, env, t, sh, r);   // (256 slots: per thread, cf. k_tick)
                 }
             }
             T::ph_stage(c, t, sh, r, fc);
@@ -976,12 +982,12 @@ template <typename K> static hipError_t resident_blocks(int *nb, K kernel, int t
 }
 
 // Resident workgroups of the persistent roll-out kernels, per DEVICE (a process may hold handles on several GPUs, and they
-// need not be the same part): [device][kernel family (12-lane / general geometry)][capacity 64 / 128] workgroups per CU + the
+// need not be the same part): [device][kernel family (12-lane / general geometry)][capacity 64 / 128 / 256] workgroups per CU + the
 // CU count, filled by the first persistent launch on that device.
 struct OccCache {
     static constexpr int MAX_DEV = 64;
     std::mutex mu;
-    int wgs[MAX_DEV][4][2] = {};       // family: 0 = k_rollout, 1 = k_rollout_geo, 2 = k_rollout_geo with the actor, 3 = k_rollout<128, 5, ..> (HOME)
+    int wgs[MAX_DEV][4][3] = {};       // family: 0 = k_rollout, 1 = k_rollout_geo, 2 = k_rollout_geo with the actor, 3 = k_rollout<128, 5, ..> (HOME)
     int n_cu[MAX_DEV] = {};
     // -> workgroups the device holds at once for (family, cap), or -1 (err set); `query` = the occupancy call of the variant
     template <typename Q>
@@ -989,7 +995,7 @@ struct OccCache {
     {
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) { err = "hipGetDevice failed"; return -1; }
-        const int ci = cap == 64 ? 0 : 1;
+        const int ci = cap == 64 ? 0 : (cap == 128 ? 1 : 2);
         std::lock_guard<std::mutex> lock(mu);
         const bool cached = dev >= 0 && dev < MAX_DEV && wgs[dev][family][ci] > 0;
         int nb = cached ? wgs[dev][family][ci] : 0, cus = cached ? n_cu[dev] : 0;
@@ -1009,6 +1015,13 @@ struct OccCache {
 static OccCache g_occ;
 
 struct Backend {
+    // the largest capacity pve_create accepts (pve_capi.inc): 256 slots for the 12-lane fast path
+    static constexpr int max_capacity = 256;
+    static int bad_cap(int cap, std::string &err)
+    {
+        err = "no kernel for capacity " + std::to_string(cap);
+        return -1;
+    }
     static int set_device(int dev, std::string &err)
     {
         int n = 0;
@@ -1070,7 +1083,9 @@ struct Backend {
     {
         hipStream_t s = (hipStream_t)stream;
         if (cap == 64) hipLaunchKernelGGL(k_tick<64>, dim3(P.n_envs), dim3(64), 0, s, c, P);
-        else hipLaunchKernelGGL(k_tick<128>, dim3(P.n_envs), dim3(128), 0, s, c, P);
+        else if (cap == 128) hipLaunchKernelGGL(k_tick<128>, dim3(P.n_envs), dim3(128), 0, s, c, P);
+        else if (cap == 256) hipLaunchKernelGGL(k_tick<256>, dim3(P.n_envs), dim3(256), 0, s, c, P);
+        else return bad_cap(cap, err);
         return check_launch(err);
     }
     static int launch_rollout(const Const &c, const Params &P_in, const RolloutArgs &R, int cap, void *stream, std::string &err)
@@ -1097,9 +1112,11 @@ struct Backend {
             if (P.phase_cycles) return 1;       // pve_debug_phase_cycles armed: the chunked launches record the cycles (as the geo path does)
 #endif
             // as many workgroups as the chip holds at once (the queue needs no more; fewer when the call has fewer items)
+            // (each capacity from its own kernel's occupancy: the 256-slot block admits half the 128-slot workgroups per CU)
             grid = g_occ.resident(0, cap, [&](int *nb) {
-                return (cap == 64) ? resident_blocks(nb, k_rollout<64, 4, false, false, false, false, true>, 64)
-                                   : resident_blocks(nb, k_rollout<128, 4, false, false, false, false, true>, 128); }, err);
+                if (cap == 64) return resident_blocks(nb, k_rollout<64, 4, false, false, false, false, true>, 64);
+                if (cap == 128) return resident_blocks(nb, k_rollout<128, 4, false, false, false, false, true>, 128);
+                return resident_blocks(nb, k_rollout<256, 4, false, false, false, false, true>, 256); }, err);
             if (grid < 0) return -1;
             const long long items = (long long)P.n_envs * (R.n_full + R.n_taper);
             if (const char *g = PVE_KNOB("PVE_PERSISTENT_GRID")) { const long long v = atoll(g); if (v > 0) grid = v; }   // A/B knob
@@ -1107,7 +1124,8 @@ struct Backend {
         } else if (P.phase_cycles) {
             // the phase-cycle diagnostics exist for the default kernel only: every other variant (table, actor, training outputs)
             // answers "no resident kernel" and the caller falls back to per-tick launches, which record the cycles
-            if (train || idt || act) return 1;
+            // (256 slots: no diagnostics variant of the resident kernel either)
+            if (train || idt || act || cap == 256) return 1;
             if (cap == 64) hipLaunchKernelGGL((k_rollout<64, 4, true>), dim3(P.n_envs), dim3(64), 0, s, c, P, Rk);
             else hipLaunchKernelGGL((k_rollout<128, 4, true>), dim3(P.n_envs), dim3(128), 0, s, c, P, Rk);
             return check_launch(err);
@@ -1135,10 +1153,12 @@ struct Backend {
             return check_launch(err);
         }
         // variant = capacity x action source (pool / zero, actor, id-indexed table) x training outputs x launch form
+        if (cap != 64 && cap != 128 && cap != 256) return bad_cap(cap, err);
 #define PVE_ROLLOUT(ACT_, TRAIN_, IDT_, PERS_)                                                                                           \
         do {                                                                                                                             \
             if (cap == 64) hipLaunchKernelGGL((k_rollout<64, 4, false, ACT_, TRAIN_, IDT_, PERS_>), dim3((unsigned)grid), dim3(64), 0, s, c, P, Rk);  \
-            else hipLaunchKernelGGL((k_rollout<128, 4, false, ACT_, TRAIN_, IDT_, PERS_>), dim3((unsigned)grid), dim3(128), 0, s, c, P, Rk);          \
+            else if (cap == 128) hipLaunchKernelGGL((k_rollout<128, 4, false, ACT_, TRAIN_, IDT_, PERS_>), dim3((unsigned)grid), dim3(128), 0, s, c, P, Rk);  \
+            else hipLaunchKernelGGL((k_rollout<256, 4, false, ACT_, TRAIN_, IDT_, PERS_>), dim3((unsigned)grid), dim3(256), 0, s, c, P, Rk);          \
         } while (0)
 #define PVE_ROLLOUT_SRC(TRAIN_, PERS_)                                                                                                   \
         do {                                                                                                                             \
@@ -1160,6 +1180,7 @@ struct Backend {
         const bool act = R.source == 2 /* PVE_SRC_ACTOR */;
         if (off || P_in.phase_cycles || (train && R.source == 3)) return 1;
         if (act && (act_off || R.exact_f32 || (R.queue && !R.actor_actions))) return 1;
+        if (cap != 64 && cap != 128) return bad_cap(cap, err);         // (the 4- / 8-lane layouts: 64 or 128 slots)
         const bool fix4 = g.lane_num == 4;           // (the 4-lane layout's far-conflict path is a kernel of its own)
         // (the closed loop with the training outputs is bound by the state writes: its queue form measured 130 against 128 us per
         //  tick of chunked launches, so it stays on those.  Round 6: the 4-lane <TRAIN, PERS> variant is instantiated -- it
@@ -1222,6 +1243,7 @@ struct Backend {
     static int launch_tick_geo(const GeoConst &g, const Params &P, int cap, void *stream, std::string &err)
     {
         hipStream_t s = (hipStream_t)stream;
+        if (cap != 64 && cap != 128) return bad_cap(cap, err);         // (the 4- / 8-lane layouts: 64 or 128 slots)
         // (the 4-lane layout's far-conflict path is a kernel of its own: FIX4)
         if (g.lane_num == 4) {
             if (P.phase_cycles) {                                    // diagnostics build (pve_debug_phase_cycles)
@@ -1241,14 +1263,17 @@ struct Backend {
         hipStream_t s = (hipStream_t)stream;
         const int blocks = (P.n_envs + 63) / 64;
         if (cap == 64) hipLaunchKernelGGL(k_reset_geo<64>, dim3(blocks), dim3(64), 0, s, g, P, 200000);
-        else hipLaunchKernelGGL(k_reset_geo<128>, dim3(blocks), dim3(64), 0, s, g, P, 200000);
+        else if (cap == 128) hipLaunchKernelGGL(k_reset_geo<128>, dim3(blocks), dim3(64), 0, s, g, P, 200000);
+        else return bad_cap(cap, err);
         return check_launch(err);
     }
     static int launch_compact(const Params &P, int cap, void *stream, std::string &err)
     {
         hipStream_t s = (hipStream_t)stream;
         if (cap == 64) hipLaunchKernelGGL(k_compact<64>, dim3(P.n_envs), dim3(64), 0, s, P);
-        else hipLaunchKernelGGL(k_compact<128>, dim3(P.n_envs), dim3(128), 0, s, P);
+        else if (cap == 128) hipLaunchKernelGGL(k_compact<128>, dim3(P.n_envs), dim3(128), 0, s, P);
+        else if (cap == 256) hipLaunchKernelGGL(k_compact<256>, dim3(P.n_envs), dim3(256), 0, s, P);
+        else return bad_cap(cap, err);
         return check_launch(err);
     }
     static int pack_actor(const float *W, float *flat, unsigned char *packed, void *stream, std::string &err)
@@ -1269,16 +1294,19 @@ struct Backend {
         const int grid = (n_envs + 3) / 4 < wgs ? (n_envs + 3) / 4 : wgs;
         if (exact_f32) {
             if (cap == 64) hipLaunchKernelGGL((k_actor_t<64, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs);
-            else hipLaunchKernelGGL((k_actor_t<128, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs);
+            else if (cap == 128) hipLaunchKernelGGL((k_actor_t<128, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs);
+            else hipLaunchKernelGGL((k_actor_t<256, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs);
         } else {
             if (cap == 64) hipLaunchKernelGGL((k_actor_h<64, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs);
-            else hipLaunchKernelGGL((k_actor_h<128, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs);
+            else if (cap == 128) hipLaunchKernelGGL((k_actor_h<128, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs);
+            else hipLaunchKernelGGL((k_actor_h<256, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs);
         }
     }
     static int launch_actor(const float *W, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
                             double *actions, int n_envs, int cap, void *stream, std::string &err)
     {
         hipStream_t s = (hipStream_t)stream;
+        if (cap != 64 && cap != 128 && cap != 256) return bad_cap(cap, err);
         if (mode & 1) launch_actor_t<float>(W, packed, (const float *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, s);
         else launch_actor_t<double>(W, packed, (const double *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, s);
         return check_launch(err);
@@ -1287,7 +1315,9 @@ struct Backend {
     {
         hipStream_t s = (hipStream_t)stream;
         if (cap == 64) hipLaunchKernelGGL(k_probe<64>, dim3(P.n_envs), dim3(64), 0, s, P, sink);
-        else hipLaunchKernelGGL(k_probe<128>, dim3(P.n_envs), dim3(128), 0, s, P, sink);
+        else if (cap == 128) hipLaunchKernelGGL(k_probe<128>, dim3(P.n_envs), dim3(128), 0, s, P, sink);
+        else if (cap == 256) hipLaunchKernelGGL(k_probe<256>, dim3(P.n_envs), dim3(256), 0, s, P, sink);
+        else return bad_cap(cap, err);
         return check_launch(err);
     }
     static int launch_reset(const Const &c, const Params &P, int cap, void *stream, std::string &err)
@@ -1295,7 +1325,9 @@ struct Backend {
         hipStream_t s = (hipStream_t)stream;
         const int blocks = (P.n_envs + 63) / 64;
         if (cap == 64) hipLaunchKernelGGL(k_reset<64>, dim3(blocks), dim3(64), 0, s, c, P, 200000);
-        else hipLaunchKernelGGL(k_reset<128>, dim3(blocks), dim3(128 / 2), 0, s, c, P, 200000);
+        else if (cap == 128) hipLaunchKernelGGL(k_reset<128>, dim3(blocks), dim3(128 / 2), 0, s, c, P, 200000);
+        else if (cap == 256) hipLaunchKernelGGL(k_reset<256>, dim3(blocks), dim3(64), 0, s, c, P, 200000);
+        else return bad_cap(cap, err);
         return check_launch(err);
     }
 };

@@ -93,6 +93,7 @@ template <int NW> PVE_HD int mask_below(const u64 *m, int t)   // set bits at po
 template <int NW> PVE_HD int mask_rank(const u64 *m, int t)
 {
 #if PVE_DEVICE_CODE
+    if constexpr (NW <= 2) {
     // (NW <= 2; both words are read and selected: m may live in registers, where a per-lane index would go through scratch)
     const u64 w0 = m[0], w1 = m[NW - 1];
     const bool up = NW > 1 && t >= 64;
@@ -100,6 +101,21 @@ template <int NW> PVE_HD int mask_rank(const u64 *m, int t)
     int c = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(w >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)w, 0u));
     c += up ? __builtin_popcountll(w0) : 0;
     return c;
+    } else {
+        // NW = 4 (CAP = 256): the wave's own word selected by t >> 6, the full words below it popcounted; every word is read
+        // and selected, as above
+        static_assert(NW == 4, "mask_rank: 64, 128 or 256 slots");
+        const int wi = t >> 6;
+        u64 w = m[0];
+        int c = 0;
+#pragma unroll
+        for (int k = 1; k < NW; k++) {
+            const u64 mk = m[k];
+            c += wi >= k ? __builtin_popcountll(m[k - 1]) : 0;
+            w = wi == k ? mk : w;
+        }
+        return c + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(w >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)w, 0u));
+    }
 #else
     return mask_below<NW>(m, t);
 #endif
@@ -355,6 +371,11 @@ PVE_HD int mad24(int a, int b, int c)
 }
 
 // ------------------------------------------------------------------ shared (LDS) block of one env
+// A stored slot index, or a value that can reach CAP (a sentinel, a count of slots): one byte up to 128 slots, two at 256.
+// SLOT_NONE<CAP> marks "no slot" where a real slot could otherwise collide with the sentinel (255 is a slot at 256).
+template <int CAP> using slot_t = typename std::conditional<(CAP <= 128), uint8_t, uint16_t>::type;
+// (a variable, not a constexpr function: a call is folded only after inlining, which re-orders the code of the existing kernels)
+template <int CAP> constexpr int SLOT_NONE = CAP <= 128 ? 255 : 0xFFFF;
 // HOME (k_rollout<128, 5, ..>: the 96-register / 10-workgroups-per-CU build of the resident kernel): the per-slot state lives
 // in LDS, registers hold it only inside the phase that works on it.  The fields that are merely CARRIED through most of the
 // tick -- jerk_sum, closer_p, id, seq_in_lane | id_info[1], count -- have arrays of their own: FX updates count / jerk_sum in
@@ -366,6 +387,7 @@ PVE_HD int mad24(int a, int b, int c)
 // at <= 15 360 B (tools/occupancy_probe.hip; the runtime's occupancy query says ten up to 16 384 B, the hardware starts nine).
 // BUILD .. WALK run in passes over groups of lists when a tick needs more entries than the pool holds.
 template <int CAP> struct Homes {
+    static_assert(CAP <= 128, "HOME: id_info[1] is packed into one byte of h_sv (no HOME build at 256 slots)");
     double h_jerk_sum[CAP], h_closer[CAP];
     int h_id[CAP], h_sv[CAP], h_count[CAP];          // h_sv = seq_in_lane << 8 | id_info[1] (id_info[1] < CAP <= 128, rows < 2^23)
 };
@@ -418,13 +440,14 @@ struct Shared : std::conditional<HOME_, Homes<CAP>, HomesOff<CAP>>::type {
     // k_rollout, LOCK2 -> FIN: kept vehicles below every slot (index CAP: all of them), so that FIN's new lane starts and the
     // dense threads' new slots are one read each instead of a two-word popcount; lives behind the 2 CAP ints of the EARLY
     // staging in the sorted-list storage (dead since WALK)
-    PVE_HD uint8_t *keep_pre() { return DIRECT ? (uint8_t *)s_vd + 7 * CAP * 4 : (uint8_t *)s_idx + 2 * CAP * 4; }
+    // (entry CAP is a count of up to CAP: slot_t, two bytes at 256 slots)
+    PVE_HD slot_t<CAP> *keep_pre() { return (slot_t<CAP> *)(DIRECT ? (uint8_t *)s_vd + 7 * CAP * 4 : (uint8_t *)s_idx + 2 * CAP * 4); }
     // FX -> LOCK: what FX decided about the reward of the vehicle in slot t (0 = keep, 1 = -10, 2 = +5), for the dense
     // thread that holds the reward; u_list[CAP ..) is free between RANK and the EARLY staging of FIN
     PVE_HD uint8_t *fxcode() { return u_list + CAP; }
     // FX -> LOCK: the virtual-header pointers as a byte chain for the dead-lock walk: chain[s] = header of slot s, CAP = none;
-    // chain[CAP] = CAP (sentinel).  u_slot is free between REWARD and FIN's staging
-    PVE_HD uint8_t *chain() { return u_slot; }
+    // chain[CAP] = CAP (sentinel; slot_t: two bytes at 256 slots).  u_slot is free between REWARD and FIN's staging
+    PVE_HD slot_t<CAP> *chain() { return (slot_t<CAP> *)u_slot; }
     template <int K> PVE_HD int *sti()   // K = I_ID .. I_HDR
     {
         if (DIRECT) return (int *)s_vd + K * CAP;
@@ -485,6 +508,13 @@ struct Shared : std::conditional<HOME_, Homes<CAP>, HomesOff<CAP>>::type {
     alignas(4) uint8_t l2lp[NL][4];  // lane2lane[d][k] (15 = none) | our position inside lane2lane[that lane] << 4 | (that lane % 3) << 6
                                      // (rows are read as one dword; the high nibble IS the index m * 4 + position into tabA / B / C)
     int lead_n;                      // scratch units claimed by the dead-lock cycles
+    // the overlays above, with their sizes (slot_t widens chain / keep_pre at 256 slots)
+    static_assert(POOL < (1 << 16), "s_idx: entry | tag << 16");
+    static_assert((CAP + 1) * sizeof(slot_t<CAP>) <= POOL, "chain() in u_slot");
+    static_assert(HOME_ || 5 * CAP <= POOL, "stf<>(): the EARLY staging doubles in u_vd[0 .. 5 CAP)");
+    static_assert(DIRECT || HOME_ || (CAP * 4 <= POOL && CAP + CAP * 4 <= POOL), "sti<5>() in u_slot, sti<6>() in u_list[CAP ..)");
+    static_assert(DIRECT ? 7 * CAP * 4 + (CAP + 1) * sizeof(slot_t<CAP>) <= POOL * sizeof(double)
+                         : 2 * CAP * 4 + (CAP + 1) * sizeof(slot_t<CAP>) <= POOL * 4, "keep_pre() behind the EARLY staging ints");
 };
 
 struct Regs {
@@ -498,7 +528,7 @@ struct Regs {
     int hdr;
     int hit, coll_seen, coll_fin;
     int alive, ctl, del, fin;
-    int cyc;                         // dead-lock cycle membership: bit0 | len << 1 | rank << 5 | leader slot << 9
+    int cyc;                         // dead-lock cycle membership: bit0 | len << 1 | rank << 5 | leader slot << 9 (slot < 256: 17 bits)
     int intent, route, ord;          // general-geometry path only (intention, direction[lane][intention], processing order)
     int mmask;                       // general-geometry path only: bit d = member of list d (COUNT .. FILL)
     // dense mapping (12-lane kernels): thread t = the t-th controlled vehicle of the intersection.  reward / kr / kv / hdr /
@@ -1510,8 +1540,8 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
         sh.fxcode()[t] = (uint8_t)code;
         {                                                 // (after this thread's own resets of hdr[t] above)
             const int h = sh.hdr[t];
-            sh.chain()[t] = (uint8_t)(h < 0 ? CAP : h);
-            if (t == 0) sh.chain()[CAP] = (uint8_t)CAP;
+            sh.chain()[t] = (slot_t<CAP>)(h < 0 ? CAP : h);
+            if (t == 0) sh.chain()[CAP] = (slot_t<CAP>)CAP;
         }
         {
             u64 *const ms[5] = {sh.m_del, sh.m_fin, sh.m_ctlnow, sh.m_coll, sh.m_spawn};
@@ -1569,7 +1599,7 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
 #else
             // straight-line: the chain table (FX) maps "no header" and the sentinel to the sentinel, so ten unconditional
             // byte reads never leave it; the first return to s0 sets len and parks the walk on the sentinel
-            const uint8_t *ch = sh.chain();
+            const auto *ch = sh.chain();
 #pragma unroll
             for (int hop = 0; hop < 10; hop++) {                                  // ref :1470-1478
                 cur = ch[cur];
@@ -1614,8 +1644,8 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
         u64 keep[NW];
 #pragma unroll
         for (int k = 0; k < NW; k++) keep[k] = sh.m_alive[k] & ~sh.m_del[k];
-        sh.keep_pre()[t] = (uint8_t)mask_rank<NW>(keep, t);
-        if (t == 0) sh.keep_pre()[CAP] = (uint8_t)mask_count<NW>(keep);
+        sh.keep_pre()[t] = (slot_t<CAP>)mask_rank<NW>(keep, t);
+        if (t == 0) sh.keep_pre()[CAP] = (slot_t<CAP>)mask_count<NW>(keep);
     }
     // the same two phases with everything per slot (general-geometry kernel: no dense mapping there)
     static PVE_HD void ph_lock_slot(const PVE_AS4 Const &c, int t, Sh &sh, Regs &r)
@@ -1635,7 +1665,7 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
             // the smallest slot and its rank in the sorted record list
             int cur = t, len = 0, mn = t, rank = 0;
             {                                             // straight-line over the byte chain written in FX (cf. ph_lock)
-                const uint8_t *ch = sh.chain();
+                const auto *ch = sh.chain();         // (SharedGeo: bytes; Shared<CAP>: slot_t<CAP>)
 #pragma unroll
                 for (int hop = 0; hop < 10; hop++) {                              // ref :1470-1478
                     cur = ch[cur];
@@ -2190,6 +2220,7 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
     static PVE_HD void ph_state_publish(const OutT &O, int t, Sh &sh, const Regs &r)
     {
         static_assert(!Sh::HOME, "the HOME block keeps vir_dis in virdis[]: no training outputs through it");
+        static_assert(CAP <= 128, "a descriptor byte is slot | fresh << 7: 256 slots write the states per thread (ph_state)");
         if (!O.state_pre || !r.dctl) return;
         uint8_t *desc = (uint8_t *)sh.virdis + 8 * t;
         const int sl = r.ds;

@@ -45,7 +45,7 @@ def main():
     ap.add_argument("--weights", required=True, help=".npz with the 12 actor tensors (tools/extract_actor.py)")
     ap.add_argument("--ticks", type=int, default=1000)
     ap.add_argument("--envs", type=int, default=1)
-    ap.add_argument("--capacity", type=int, default=128)
+    ap.add_argument("--capacity", type=int, default=128, help="slots per intersection: 64, 128 or 256 (256: lane_num 12)")
     ap.add_argument("--vm", type=float, default=5.0)
     ap.add_argument("--lane-num", type=int, default=12, choices=(12, 8, 4), help="main.py --lane_num (:101)")
     ap.add_argument("--seed", type=int, default=20250213, help="synthetic streams / 8-lane intention draws")

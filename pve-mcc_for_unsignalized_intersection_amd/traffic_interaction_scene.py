@@ -84,7 +84,7 @@ class TrafficInteraction:
 
     # ------------------------------------------------------------------ view maintenance
     def _refresh(self, states=None):
-        """Rebuild veh_info[lane][ind] from the device state (one D2H read of a <= 128-slot env)."""
+        """Rebuild veh_info[lane][ind] from the device state (one D2H read of a <= 256-slot env)."""
         b = self._b
         info = b.read_env(0)
         vehs = b.read_vehicles(0)
