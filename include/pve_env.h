@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PVE_ABI_VERSION 8
+#define PVE_ABI_VERSION 9
 #define PVE_LANES 12          /* physical lanes: lane_num = 4, 8 or 12 (arrays are padded to 12) */
 #define PVE_MAX_DIRS 16       /* virtual-lane lists (routes): 12 for lane_num 4 / 12, 16 for lane_num 8 (ref :86, :132, :167) */
 #define PVE_OBS_WIDTH 28      /* (o_agent_num + 1) * 4, ref :1295 */
@@ -206,6 +206,27 @@ int pve_actor_forward(pve_handle h, const float *weights, const void *obs /* flo
  * never reads observations) unless out->state_pre is requested, which needs the previous rows (obs_prev_post). */
 int pve_step_all_actor(pve_handle h, const float *weights, const void *obs_in, double *actions,
                        const pve_outputs *out);
+
+/* Exploration noise of the device actor (reference main.py:44, :239: the training loop commands
+ * `agent.action(state) + np.random.randn(1) * noise_range` for every controlled vehicle, every tick; the evaluation loops run
+ * with noise_range = 0).  Opt-in, host-only state of the handle, in force from the next call:
+ *   a_cmd(env, vehicle, tick) = (double) actor_f32(row) + sigma * z(seed, env_global, vehicle_id, tick)
+ * for every controlled vehicle (a vehicle spawned at the end of the previous tick, whose row is all zero, included), 0 for every
+ * other slot as before (main.py:401); the tick clips a_cmd to [am, aM] as always (ref :1502).  It applies wherever the library
+ * runs the actor -- pve_actor_forward (the returned actions are the noisy ones), pve_step_all_actor, pve_step_many(PVE_SRC_ACTOR)
+ * in every launch form -- and never to actions the caller supplies (pve_step_all, PVE_SRC_POOL / TABLE / ZERO).
+ * z is a pure function of its four arguments (csrc/pve_noise.h; the same numbers whatever the slot, launch form, capacity, chunking
+ * or sub-batching):
+ *   vehicle_id = the vehicle's id (pve_vehicle.id, state field "id"); tick = ticks the handle has run since pve_reset when the
+ *   action is applied (the first tick after pve_reset is tick 0); env_global = env index in the handle + env_offset (a batch cut
+ *   into several handles passes each piece its first global index and draws what the uncut batch draws).
+ *   Bits: Philox4x32-10 with counter = (vehicle_id, tick mod 2^32, env_global low word, env_global high word) and
+ *   key = (seed low word, seed high word); z = sqrt(-2 ln u1) cos(2 pi u2), u = (word + 0.5) 2^-32 from output words 0 and 1,
+ *   evaluated in float64 with + - * / sqrt only in the order csrc/pve_noise.h writes down (bit-reproducible on the host:
+ *   pve_mcc_amd/noise.py).
+ * sigma = 0 switches the noise off (the default; every result is then what it was without this call).  sigma < 0, NaN or inf:
+ * PVE_ERR_INVALID; sigma > 0 on a backend without the noisy actor kernels: PVE_ERR_INVALID. */
+int pve_set_action_noise(pve_handle h, double sigma, uint64_t seed, int64_t env_offset);
 
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly

@@ -117,6 +117,7 @@ class BatchedIntersections:
         self._zero_actions = torch.zeros(E, K, dtype=torch.float64, device=dev)
         self.ticks = 0
         self._is_reset = False
+        self.exploration = (0.0, 0, 0)       # (sigma, seed, env_offset): set_exploration
 
     # ------------------------------------------------------------------ plumbing
     def _stream_ptr(self):
@@ -265,8 +266,19 @@ class BatchedIntersections:
             # copied into the handle's workspace (flat + packed for the matrix cores) on the handle's stream
             check(self.lib, self.lib.pve_set_actor(self._h, C.c_void_p(self._actor_w.data_ptr())), "pve_set_actor")
 
+    def set_exploration(self, sigma, seed=0, env_offset=0):
+        """Exploration noise of the device actor (main.py:44, :239): from the next call on, every controlled vehicle's action
+        in act(), step_with_actor() and step_many(source="actor") is float64(actor(row)) + sigma * z, with
+        z = noise.action_noise(seed, env + env_offset, vehicle id, ticks since reset()) -- reproducible, and the same in
+        every launch form.  sigma = 0 (the default state) switches it off.  env_offset: global index of this batch's first
+        environment when the batch is a piece of a larger one.  Actions passed to step() are never touched."""
+        check(self.lib, self.lib.pve_set_action_noise(self._h, float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)),
+              "pve_set_action_noise")
+        self.exploration = (float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset))
+
     def act(self):
-        """actions [n_envs, capacity] = actor(obs) for the controlled slots, 0 elsewhere (device tensor)."""
+        """actions [n_envs, capacity] = actor(obs) for the controlled slots (+ the exploration noise, set_exploration),
+        0 elsewhere (device tensor)."""
         self.lib.pve_set_stream(self._h, self._stream_ptr())
         check(self.lib, self.lib.pve_actor_forward(self._h, None, C.c_void_p(self.obs.data_ptr()),
                                                    C.c_void_p(self._actor_actions.data_ptr())), "pve_actor_forward")
@@ -589,6 +601,12 @@ class PipelinedIntersections:
         for k, sub in enumerate(self.subs):
             with self._on(k):
                 sub.set_actor(weights)
+
+    def set_exploration(self, sigma, seed=0):
+        """BatchedIntersections.set_exploration for every sub-batch, each with the global index of its first environment:
+        the pieces draw the noise one batch of n_envs environments draws."""
+        for k, sub in enumerate(self.subs):
+            sub.set_exploration(sigma, seed, env_offset=self.bounds[k])
 
     def step_with_actor(self):
         return [sub.step_with_actor() for sub in self.subs]

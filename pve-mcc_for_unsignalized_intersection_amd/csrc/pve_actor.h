@@ -7,6 +7,7 @@
 // contraction (2 x 5 952 flop per controlled vehicle), unlike the tick.
 #pragma once
 #include "pve_types.h"
+#include "pve_noise.h"
 
 namespace pve {
 
@@ -95,6 +96,14 @@ inline float actor_canonical(const float *W, const float *x)
 }
 
 #if defined(__HIPCC__)
+// What the stand-alone actor kernels store for a controlled vehicle: the actor's output, plus the exploration noise of
+// pve_set_action_noise when it is on (uniform test; `ids` = the [n_envs][cap] id field, read only then).  main.py:44
+__device__ __forceinline__ double actor_commanded(double a, const ActionNoise &nz, int env, const int32_t *ids, size_t g)
+{
+    if (nz.sigma != 0) a = action_with_noise(a, nz, (int64_t)env + nz.env_offset, ids[g], nz.tick0);
+    return a;
+}
+
 
 // ------------------------------------------------------------------------------------------------------
 // k_actor_t: the network on the matrix cores in the TRANSPOSED form H^T = W^T X^T.  v_mfma_f32_16x16x4_f32 is an exact
@@ -154,7 +163,7 @@ __device__ __forceinline__ void actor_ln_relu16_lds(pve_v4f (&v)[4], const float
 template <int CAP, typename OBS_T>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_actor_t(const float *__restrict__ W, const OBS_T *__restrict__ obs,
                                                  const int32_t *__restrict__ meta, double *__restrict__ actions,
-                                                 int n_envs)
+                                                 int n_envs, const int32_t *__restrict__ ids, const ActionNoise nz)
 {
     __shared__ float Ws1[ACT_IN][ACT_WPAD], Ws2[ACT_H][ACT_WPAD];
     __shared__ __attribute__((aligned(16))) float Wsm[SM_TOTAL];
@@ -284,7 +293,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                 for (int r = 0; r < 4; r++) part = fmaf(g[m][r], w3[r], part);
             }
             const float a = 3.0f * tanhf(actor_xsum(part) + Wsm[SM_B3]);
-            if (q == 0 && valid) actions[base + cur_slot] = (double)a;
+            if (q == 0 && valid) actions[base + cur_slot] = actor_commanded((double)a, nz, env, ids, base + cur_slot);
         }
     }
 }
@@ -559,7 +568,7 @@ __global__ __launch_bounds__(256) void k_actor_pack(const float *__restrict__ W,
 template <int CAP, typename OBS_T>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_actor_h(const unsigned char *__restrict__ packed, const OBS_T *__restrict__ obs,
                                                  const int32_t *__restrict__ meta, double *__restrict__ actions,
-                                                 int n_envs)
+                                                 int n_envs, const int32_t *__restrict__ ids, const ActionNoise nz)
 {
     __shared__ __attribute__((aligned(64))) unsigned char sp[AP_BYTES_PADDED];
     __shared__ unsigned char slot_of_s[4][CAP];
@@ -601,7 +610,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             float x[16];
             actor_fetch(obs, base + slot, hf, x);
             const float a = actor_tile32(A1, A2, prm + wo, x, lane);
-            if (valid && hf == 0) actions[base + slot] = (double)a;
+            if (valid && hf == 0) actions[base + slot] = actor_commanded((double)a, nz, env, ids, base + slot);
         }
     }
 }

@@ -22,6 +22,15 @@
 //     static int   launch_actor(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
 //                               double *actions, int n_envs, int cap, void *stream, std::string &err);
 //     static constexpr int max_capacity = 256;   // optional: the largest capacity it runs (default 128, see backend_max_capacity)
+//     static int   launch_actor_noisy(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
+//                                     const int32_t *ids, const pve::ActionNoise &nz, double *actions, int n_envs, int cap,
+//                                     void *stream, std::string &err);
+//     static int   launch_rollout_noisy(const pve::Const &, const pve::Params &, const pve::RolloutArgs &, const pve::ActionNoise &,
+//                                       int cap, void *stream, std::string &err);
+//     static int   launch_rollout_geo_noisy(const pve::GeoConst &, const pve::Params &, const pve::RolloutArgs &,
+//                                           const pve::ActionNoise &, int cap, void *stream, std::string &err);
+//                                                // optional, all three or none: launch_actor / launch_rollout / launch_rollout_geo +
+//                                                // the exploration noise of pve_set_action_noise (ActionNoise::tick0 = first tick)
 //   };
 //
 // pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
@@ -138,6 +147,44 @@ static bool capacity_known(int capacity)
     return capacity == 64 || capacity == 128 || (capacity == 256 && backend_max_capacity<Backend>::value >= 256);
 }
 
+// Exploration noise (pve_set_action_noise) needs kernels that draw it: Backend::launch_actor_noisy / launch_rollout_noisy /
+// launch_rollout_geo_noisy (detected by the first).  A backend without them runs the actor as before and pve_set_action_noise
+// refuses sigma > 0.
+template <class B, class = void> struct backend_noise {
+    static constexpr bool value = false;
+    static int launch_actor(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta, const int32_t *,
+                            const ActionNoise &, double *actions, int n_envs, int cap, void *stream, std::string &err)
+    {
+        return B::launch_actor(flat, packed, obs, mode, meta, actions, n_envs, cap, stream, err);
+    }
+    static int launch_rollout(const Const &c, const Params &P, const RolloutArgs &R, const ActionNoise &, int cap, void *stream, std::string &err)
+    {
+        return B::launch_rollout(c, P, R, cap, stream, err);
+    }
+    static int launch_rollout_geo(const GeoConst &g, const Params &P, const RolloutArgs &R, const ActionNoise &, int cap, void *stream,
+                                  std::string &err)
+    {
+        return B::launch_rollout_geo(g, P, R, cap, stream, err);
+    }
+};
+template <class B> struct backend_noise<B, decltype((void)&B::launch_actor_noisy)> {
+    static constexpr bool value = true;
+    static int launch_actor(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta, const int32_t *ids,
+                            const ActionNoise &nz, double *actions, int n_envs, int cap, void *stream, std::string &err)
+    {
+        if (nz.sigma == 0) return B::launch_actor(flat, packed, obs, mode, meta, actions, n_envs, cap, stream, err);
+        return B::launch_actor_noisy(flat, packed, obs, mode, meta, ids, nz, actions, n_envs, cap, stream, err);
+    }
+    static int launch_rollout(const Const &c, const Params &P, const RolloutArgs &R, const ActionNoise &nz, int cap, void *stream, std::string &err)
+    {
+        return B::launch_rollout_noisy(c, P, R, nz, cap, stream, err);
+    }
+    static int launch_rollout_geo(const GeoConst &g, const Params &P, const RolloutArgs &R, const ActionNoise &nz, int cap, void *stream,
+                                  std::string &err)
+    {
+        return B::launch_rollout_geo_noisy(g, P, R, nz, cap, stream, err);
+    }
+};
 extern "C" {
 
 int pve_abi_version(void) { return PVE_ABI_VERSION; }
@@ -201,6 +248,7 @@ int pve_create(const pve_config *cfg, int n_envs, int capacity, int device_id, v
     h->q_done_base = 0;
     h->last_launch_kind = PVE_LAUNCH_NONE;
     h->stop_phase = -1;
+    memset(&h->noise, 0, sizeof(h->noise));
     *out = h;
     return PVE_OK;
 }
@@ -334,6 +382,21 @@ int pve_scene_update(pve_handle h, const double *actions, const pve_outputs *out
 static float *actor_flat(pve_handle h) { return (float *)(h->ws + h->L.off_actor_flat); }
 static unsigned char *actor_packed(pve_handle h) { return (unsigned char *)(h->ws + h->L.off_actor_packed); }
 
+// the handle's noise for a launch whose first action is applied at the handle's current tick
+static ActionNoise noise_now(pve_handle h)
+{
+    ActionNoise nz = h->noise;
+    nz.tick0 = (uint32_t)(unsigned long long)h->ticks_since_reset;
+    return nz;
+}
+// the stand-alone actor pass obs -> actions, with the handle's noise
+static int run_actor(pve_handle h, const void *obs, double *actions, std::string &err)
+{
+    const int32_t *meta = (const int32_t *)(h->ws + h->L.off_i32[I_META]), *ids = (const int32_t *)(h->ws + h->L.off_i32[I_ID]);
+    return backend_noise<Backend>::launch_actor(actor_flat(h), actor_packed(h), obs, actor_mode(h), meta, ids, noise_now(h), actions,
+                                                h->n_envs, h->cap, h->stream, err);
+}
+
 int pve_set_actor(pve_handle h, const float *weights)
 {
     if (!h || !weights) return fail(PVE_ERR_INVALID, "pve_set_actor: null argument");
@@ -361,10 +424,18 @@ int pve_actor_forward(pve_handle h, const float *weights, const void *obs, doubl
     if (rc != PVE_OK) return rc;
     DevScope dev_scope(h->device);
     std::string err;
-    const int32_t *meta = (const int32_t *)(h->ws + h->L.off_i32[I_META]);
-    if (Backend::launch_actor(actor_flat(h), actor_packed(h), obs, actor_mode(h), meta, actions, h->n_envs, h->cap,
-                              h->stream, err) != 0)
-        return fail(PVE_ERR_NO_DEVICE, "pve_actor_forward: " + err);
+    if (run_actor(h, obs, actions, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_actor_forward: " + err);
+    return PVE_OK;
+}
+
+int pve_set_action_noise(pve_handle h, double sigma, uint64_t seed, int64_t env_offset)
+{
+    if (!h) return fail(PVE_ERR_INVALID, "pve_set_action_noise: null handle");
+    if (!(sigma >= 0) || sigma > 1.7976931348623157e308)
+        return fail(PVE_ERR_INVALID, "pve_set_action_noise: sigma must be finite and >= 0");
+    if (sigma > 0 && !backend_noise<Backend>::value)
+        return fail(PVE_ERR_INVALID, "pve_set_action_noise: this backend has no noisy actor kernels (sigma must be 0)");
+    h->noise.sigma = sigma; h->noise.seed = seed; h->noise.env_offset = env_offset;
     return PVE_OK;
 }
 
@@ -430,8 +501,9 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
         R.queue = (unsigned *)(h->ws + h->L.off_queue);
         R.n_shards = Backend::n_xcc(h->device);
         R.done_base = h->q_done_base;
-        const int rr = h->geo ? Backend::launch_rollout_geo(h->g, P, R, h->cap, h->stream, err)
-                              : Backend::launch_rollout(h->c, P, R, h->cap, h->stream, err);
+        const ActionNoise nz = noise_now(h);       // (read by the actor variants only)
+        const int rr = h->geo ? backend_noise<Backend>::launch_rollout_geo(h->g, P, R, nz, h->cap, h->stream, err)
+                              : backend_noise<Backend>::launch_rollout(h->c, P, R, nz, h->cap, h->stream, err);
         if (rr < 0) { (void)queue_reset(h); return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err); }
         if (rr == 0) {
             h->q_done_base += (unsigned)(R.n_full + R.n_taper);
@@ -463,8 +535,9 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
             R.prev_rows = o0.obs_prev_post;
             if (k0 > 0 && ro->trajectory) { Outputs prev; shift_outputs(prev, o0, k0 - 1, E, cap, f32); R.prev_rows = prev.obs_post; }
             if (ro->trajectory) shift_outputs(P.out, o0, k0, E, cap, f32);
-            const int rr = h->geo ? Backend::launch_rollout_geo(h->g, P, R, h->cap, h->stream, err)
-                                  : Backend::launch_rollout(h->c, P, R, h->cap, h->stream, err);
+            const ActionNoise nz = noise_now(h);   // (ticks_since_reset moves with every chunk; read by the actor variants only)
+            const int rr = h->geo ? backend_noise<Backend>::launch_rollout_geo(h->g, P, R, nz, h->cap, h->stream, err)
+                                  : backend_noise<Backend>::launch_rollout(h->c, P, R, nz, h->cap, h->stream, err);
             if (rr < 0) return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err);
             if (rr > 0) {
                 if (ro->source == PVE_SRC_TABLE)
@@ -488,10 +561,7 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
         if (ro->source == PVE_SRC_POOL)
             P.actions = ro->pool + (size_t)(((long long)ro->pool_tick0 + k) % ro->n_pool) * (size_t)(E * cap);
         else if (ro->source == PVE_SRC_ACTOR) {
-            const int32_t *meta = (const int32_t *)(h->ws + h->L.off_i32[I_META]);
-            if (Backend::launch_actor(actor_flat(h), actor_packed(h), obs_in, actor_mode(h), meta, ro->actor_actions, h->n_envs,
-                                      h->cap, h->stream, err) != 0)
-                return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err);
+            if (run_actor(h, obs_in, ro->actor_actions, err) != 0) return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err);
             P.actions = ro->actor_actions;
             obs_in = P.out.obs_post;
         }

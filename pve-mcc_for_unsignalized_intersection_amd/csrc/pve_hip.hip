@@ -157,6 +157,20 @@ __device__ __forceinline__ void rollout_actor(const unsigned char *packed, const
     }
 }
 
+// k_rollout<.., ACT> / k_rollout_geo<.., ACT>: the exploration noise of pve_set_action_noise (pve_noise.h; main.py:44), added at the
+// intake of a tick -- the slot's own thread holds this tick's action (from LOAD, RELOAD or the queue's hand-off buffer, which
+// therefore keeps clean actor outputs), the vehicle's id and its controlled bit, and nothing else of the tick is live yet.
+// `tick` = the tick's index within the call; the same float64 expression as the stand-alone kernels (actor_commanded), so every
+// launch form commands the same bits.  The test on sigma is uniform: with the noise off a tick pays one scalar compare.
+__device__ __forceinline__ void rollout_noise(const PVE_AS4 RolloutArgsNoisy &R, int env, int tick, Regs &r)
+{
+    const double sigma = R.noise.sigma;
+    if (__builtin_expect(sigma != 0, 0)) {          // (laid out behind the loop: with the noise off the tick's code stays contiguous)
+        if (r.alive && (r.meta & M_CONTROL))
+            r.act = r.act + sigma * action_noise_z(R.noise.seed, (int64_t)env + R.noise.env_offset, r.id, R.noise.tick0 + (uint32_t)tick);
+    }
+}
+
 // PVE_SRC_TABLE: table[row][min(id, table_ids - 1)] -- a UNIFORM 64-bit row base plus a 32-bit lane offset (the `saddr + voffset`
 // form of a global load; the plain index is a sign extension + 64-bit multiply-add per lane); the unsigned minimum also clamps a
 // negative id (an empty slot, whose value is never used)
@@ -311,8 +325,9 @@ __device__ __forceinline__ void q_leave(const PVE_AS4 RolloutArgs &R, int t0)
 // PERS: the persistent form -- the workgroup pulls (intersection, chunk) items from the queue above; n_ticks = ticks per item.
 template <int CAP, int WPE, bool PROF = false, bool ACT = false, bool TRAIN = false, bool IDT = false, bool PERS = false>
 __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_rollout(const Const c_arg, const Params P_arg,
-                                                                                               const RolloutArgs R_arg)
+                                                                                               const typename rollout_args<ACT>::type R_arg)
 {
+    typedef typename rollout_args<ACT>::type RArgs;      // (ACT: RolloutArgs + the exploration noise)
     static_assert(!PERS || !PROF, "the persistent form has no phase-cycle diagnostics variant");
     static_assert(!(ACT && IDT), "one action source per variant");
     KernargPtr ka0_ = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -357,7 +372,7 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     {
         const PVE_AS4 Const &c = *(const PVE_AS4 Const *)ka0_;
         const PVE_AS4 Params &P = *(const PVE_AS4 Params *)(ka0_ + OFF_P);
-        const PVE_AS4 RolloutArgs &R = *(const PVE_AS4 RolloutArgs *)(ka0_ + OFF_R);
+        const PVE_AS4 RArgs &R = *(const PVE_AS4 RArgs *)(ka0_ + OFF_R);
         pool_idx = R.pool_tick0;
         n_ticks = R.n_ticks;
         const double *act0 = nullptr;
@@ -430,7 +445,7 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #endif
         const PVE_AS4 Const &c = *(const PVE_AS4 Const *)ka;
         const PVE_AS4 Params &P = *(const PVE_AS4 Params *)(ka + OFF_P);
-        const PVE_AS4 RolloutArgs &R = *(const PVE_AS4 RolloutArgs *)(ka + OFF_R);
+        const PVE_AS4 RArgs &R = *(const PVE_AS4 RArgs *)(ka + OFF_R);
         lds_barrier();
         PVE_PHASE_MARK(0)
         if constexpr (CAP == 64 && !PERS) {
@@ -448,6 +463,7 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #endif
         }
         if (k > 0) T::ph_tick_init(c, t, sh, r);
+        if constexpr (ACT) rollout_noise(R, env, k_base_ + k, r);
         T::ph_step1(c, P, env, t, sh, r);
         lds_barrier();
         PVE_PHASE_MARK(1)
@@ -588,12 +604,12 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         }
     }
     if constexpr (PERS) {
-        const PVE_AS4 RolloutArgs &R = *(const PVE_AS4 RolloutArgs *)(ka0_ + OFF_R);
+        const PVE_AS4 RArgs &R = *(const PVE_AS4 RArgs *)(ka0_ + OFF_R);
         const PVE_AS4 Params &P = *(const PVE_AS4 Params *)(ka0_ + OFF_P);
         q_publish(R, P.n_envs, t0_, env0_, chunk_);
     } else break;
   }
-    if constexpr (PERS) q_leave(*(const PVE_AS4 RolloutArgs *)(ka0_ + OFF_R), t0_);
+    if constexpr (PERS) q_leave(*(const PVE_AS4 RArgs *)(ka0_ + OFF_R), t0_);
 }
 
 // General-geometry tick (lane_num 4 / 8): same workgroup-per-intersection structure, phases of
@@ -704,8 +720,9 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu((CAP == 64 
 // row.  Every tick is staged (no `still` shortcut): the actor runs every tick.
 template <int CAP, bool FIX4 = false, int WPE = 4, bool TRAIN = false, bool IDT = false, bool PERS = false, bool ACT = false>
 __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_rollout_geo(const GeoConst g_arg, const Params P_arg,
-                                                                                                const RolloutArgs R_arg)
+                                                                                                const typename rollout_args<ACT>::type R_arg)
 {
+    typedef typename rollout_args<ACT>::type RArgs;      // (ACT: RolloutArgs + the exploration noise)
     static_assert(!(TRAIN && IDT), "lane_num 4 / 8: the table source without the training outputs");
     static_assert(!ACT || !IDT, "the closed loop of the geometry kernel: one action source");
     KernargPtr ka0_ = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -729,7 +746,7 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     {
         const PVE_AS4 GeoConst &g = *(const PVE_AS4 GeoConst *)ka0_;
         const PVE_AS4 Params &P = *(const PVE_AS4 Params *)(ka0_ + OFF_P);
-        const PVE_AS4 RolloutArgs &R = *(const PVE_AS4 RolloutArgs *)(ka0_ + OFF_R);
+        const PVE_AS4 RArgs &R = *(const PVE_AS4 RArgs *)(ka0_ + OFF_R);
         pool_idx = R.pool_tick0;
         n_ticks = R.n_ticks;
         const double *act0 = nullptr;
@@ -797,9 +814,10 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 #endif
         const PVE_AS4 GeoConst &g = *(const PVE_AS4 GeoConst *)ka;
         const PVE_AS4 Params &P = *(const PVE_AS4 Params *)(ka + OFF_P);
-        const PVE_AS4 RolloutArgs &R = *(const PVE_AS4 RolloutArgs *)(ka + OFF_R);
+        const PVE_AS4 RArgs &R = *(const PVE_AS4 RArgs *)(ka + OFF_R);
         lds_barrier();
         if (k > 0) T::ph_tick_init(g, t, sh, r);      // (the list counters S1 adds to were cleared in the previous tick's FX phase)
+        if constexpr (ACT) rollout_noise(R, env, k_base_ + k, r);
         T::ph_step1(g, P, env, t, sh, r);
         lds_barrier();
         B::ph_step2(g.base, t, sh, r);
@@ -890,12 +908,12 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         B::ph_flush(P, env0_, t0_, sh);
     }
     if constexpr (PERS) {
-        const PVE_AS4 RolloutArgs &R = *(const PVE_AS4 RolloutArgs *)(ka0_ + OFF_R);
+        const PVE_AS4 RArgs &R = *(const PVE_AS4 RArgs *)(ka0_ + OFF_R);
         const PVE_AS4 Params &P = *(const PVE_AS4 Params *)(ka0_ + OFF_P);
         q_publish(R, P.n_envs, t0_, env0_, chunk_);
     } else break;
   }
-    if constexpr (PERS) q_leave(*(const PVE_AS4 RolloutArgs *)(ka0_ + OFF_R), t0_);
+    if constexpr (PERS) q_leave(*(const PVE_AS4 RArgs *)(ka0_ + OFF_R), t0_);
 }
 
 // tools/probe_kernel.sh: compile ONE variant of k_rollout / k_rollout_geo (seconds instead of minutes for the whole library) to
@@ -903,10 +921,12 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 // -DPVE_PROBE_GEO="128, true, 4, false, false, true, true"
 #if defined(PVE_PROBE_ONE) || defined(PVE_PROBE_GEO)
 #ifdef PVE_PROBE_ONE
-template __global__ void k_rollout<PVE_PROBE_ONE>(const Const, const Params, const RolloutArgs);
+template <int CAP, int WPE, bool PROF = false, bool ACT = false, bool... REST> struct probe_one_act { static constexpr bool value = ACT; };
+template __global__ void k_rollout<PVE_PROBE_ONE>(const Const, const Params, const rollout_args<probe_one_act<PVE_PROBE_ONE>::value>::type);
 #endif
 #ifdef PVE_PROBE_GEO
-template __global__ void k_rollout_geo<PVE_PROBE_GEO>(const GeoConst, const Params, const RolloutArgs);
+template <int CAP, bool FIX4 = false, int WPE = 4, bool TRAIN = false, bool IDT = false, bool PERS = false, bool ACT = false> struct probe_geo_act { static constexpr bool value = ACT; };
+template __global__ void k_rollout_geo<PVE_PROBE_GEO>(const GeoConst, const Params, const rollout_args<probe_geo_act<PVE_PROBE_GEO>::value>::type);
 #endif
 #else
 template <int CAP>
@@ -1090,12 +1110,22 @@ struct Backend {
     }
     static int launch_rollout(const Const &c, const Params &P_in, const RolloutArgs &R, int cap, void *stream, std::string &err)
     {
+        ActionNoise off;
+        memset(&off, 0, sizeof(off));
+        return launch_rollout_noisy(c, P_in, R, off, cap, stream, err);
+    }
+    // launch_rollout + the exploration noise of the actor variants (nz.tick0 = the launch's first tick; read by the ACT variants only)
+    static int launch_rollout_noisy(const Const &c, const Params &P_in, const RolloutArgs &R, const ActionNoise &nz, int cap, void *stream,
+                                    std::string &err)
+    {
         static const bool off = PVE_KNOB("PVE_NO_ROLLOUT_KERNEL") != nullptr;   // A/B knob: one launch per tick instead
         static const bool act_off = PVE_KNOB("PVE_NO_ROLLOUT_ACTOR") != nullptr;   // A/B knob: actor + tick launches instead
         if (off || (R.source == 2 /* PVE_SRC_ACTOR */ && (act_off || R.exact_f32 || P_in.phase_cycles))) return 1;
         hipStream_t s = (hipStream_t)stream;
         Params P = P_in;
-        RolloutArgs Rk = R;
+        RolloutArgsNoisy Rk;                         // (a variant without the actor receives its RolloutArgs part)
+        (RolloutArgs &)Rk = R;
+        Rk.noise = nz;
         if (R.source == 1) {
             Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
             P.actions = R.pool + (size_t)Rk.pool_tick0 * (size_t)P.n_envs * (size_t)cap;
@@ -1174,6 +1204,13 @@ struct Backend {
     }
     static int launch_rollout_geo(const GeoConst &g, const Params &P_in, const RolloutArgs &R, int cap, void *stream, std::string &err)
     {
+        ActionNoise off;
+        memset(&off, 0, sizeof(off));
+        return launch_rollout_geo_noisy(g, P_in, R, off, cap, stream, err);
+    }
+    static int launch_rollout_geo_noisy(const GeoConst &g, const Params &P_in, const RolloutArgs &R, const ActionNoise &nz, int cap,
+                                        void *stream, std::string &err)
+    {
         static const bool off = PVE_KNOB("PVE_NO_ROLLOUT_KERNEL") != nullptr;   // A/B knob: one launch per tick instead
         static const bool act_off = PVE_KNOB("PVE_NO_ROLLOUT_ACTOR") != nullptr;   // A/B knob: actor + tick launches instead
         const bool train = P_in.out.obs_pre || P_in.out.state_pre;
@@ -1188,7 +1225,9 @@ struct Backend {
         if (R.queue && train && act) return 1;
         hipStream_t s = (hipStream_t)stream;
         Params P = P_in;
-        RolloutArgs Rk = R;
+        RolloutArgsNoisy Rk;                         // (a variant without the actor receives its RolloutArgs part)
+        (RolloutArgs &)Rk = R;
+        Rk.noise = nz;
         if (R.source == 1) {
             Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
             P.actions = R.pool + (size_t)Rk.pool_tick0 * (size_t)P.n_envs * (size_t)cap;
@@ -1286,29 +1325,39 @@ struct Backend {
     }
     template <typename OBS_T>
     static void launch_actor_t(const float *W, const unsigned char *packed, const OBS_T *obs, const int32_t *meta, double *actions,
-                               int n_envs, int cap, bool exact_f32, hipStream_t s)
+                               int n_envs, int cap, bool exact_f32, const int32_t *ids, const ActionNoise &nz, hipStream_t s)
     {
         // persistent workgroups of 4 waves (the parameters are staged in LDS once per workgroup): 4 per CU, one wave
         // per intersection at a time
         static const int wgs = [] { const char *g = PVE_KNOB("PVE_ACTOR_GRID"); const int v = g ? atoi(g) : 0; return v > 0 ? v : 1024; }();
         const int grid = (n_envs + 3) / 4 < wgs ? (n_envs + 3) / 4 : wgs;
         if (exact_f32) {
-            if (cap == 64) hipLaunchKernelGGL((k_actor_t<64, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs);
-            else if (cap == 128) hipLaunchKernelGGL((k_actor_t<128, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs);
-            else hipLaunchKernelGGL((k_actor_t<256, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs);
+            if (cap == 64) hipLaunchKernelGGL((k_actor_t<64, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs, ids, nz);
+            else if (cap == 128) hipLaunchKernelGGL((k_actor_t<128, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs, ids, nz);
+            else hipLaunchKernelGGL((k_actor_t<256, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs, ids, nz);
         } else {
-            if (cap == 64) hipLaunchKernelGGL((k_actor_h<64, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs);
-            else if (cap == 128) hipLaunchKernelGGL((k_actor_h<128, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs);
-            else hipLaunchKernelGGL((k_actor_h<256, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs);
+            if (cap == 64) hipLaunchKernelGGL((k_actor_h<64, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs, ids, nz);
+            else if (cap == 128) hipLaunchKernelGGL((k_actor_h<128, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs, ids, nz);
+            else hipLaunchKernelGGL((k_actor_h<256, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs, ids, nz);
         }
     }
     static int launch_actor(const float *W, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
                             double *actions, int n_envs, int cap, void *stream, std::string &err)
     {
+        ActionNoise off;
+        memset(&off, 0, sizeof(off));
+        return launch_actor_noisy(W, packed, obs, mode, meta, nullptr, off, actions, n_envs, cap, stream, err);
+    }
+    // the actor pass + the exploration noise of pve_set_action_noise (ids = the [n_envs][cap] id field; read when nz.sigma != 0).
+    // (pve_capi.inc takes its presence for that of launch_rollout_noisy / launch_rollout_geo_noisy as well)
+    static int launch_actor_noisy(const float *W, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
+                                  const int32_t *ids, const ActionNoise &nz, double *actions, int n_envs, int cap, void *stream,
+                                  std::string &err)
+    {
         hipStream_t s = (hipStream_t)stream;
         if (cap != 64 && cap != 128 && cap != 256) return bad_cap(cap, err);
-        if (mode & 1) launch_actor_t<float>(W, packed, (const float *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, s);
-        else launch_actor_t<double>(W, packed, (const double *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, s);
+        if (mode & 1) launch_actor_t<float>(W, packed, (const float *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, ids, nz, s);
+        else launch_actor_t<double>(W, packed, (const double *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, ids, nz, s);
         return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)

@@ -139,6 +139,15 @@ struct Params {
     Outputs out;
 };
 
+// Exploration noise of the device actor (pve_set_action_noise; pve_noise.h): what a launch needs to draw it
+struct ActionNoise {
+    double sigma;                // 0 = off
+    uint64_t seed;
+    int64_t env_offset;          // env_global = env index in the handle + env_offset
+    uint32_t tick0;              // ticks run since pve_reset when the launch's first action is applied (mod 2^32)
+    uint32_t pad_;
+};
+
 // pve_step_many: action source and output addressing of a multi-tick launch (k_rollout)
 struct RolloutArgs {
     const double *pool;          // PVE_SRC_POOL: [n_pool][n_envs][cap]
@@ -161,6 +170,13 @@ struct RolloutArgs {
     double *actor_actions;       // persistent closed loop: [n_envs][cap] actions handed from one item of an intersection to the next
     unsigned long long *q_trace; // diagnostics (pve_debug_phase_cycles armed): [chunk][env][8] timestamps of every item, or null
 };
+// What the kernel variants that run the actor (k_rollout<.., ACT>, k_rollout_geo<.., ACT>) receive instead: every other variant
+// keeps RolloutArgs, so its kernel-argument segment -- and with it the offsets of the implicit arguments behind it -- stays as it is.
+struct RolloutArgsNoisy : RolloutArgs {
+    ActionNoise noise;           // added to the actor's output of every controlled vehicle; tick0 = the launch's / call's first tick
+};
+template <bool ACT> struct rollout_args { typedef RolloutArgs type; };
+template <> struct rollout_args<true> { typedef RolloutArgsNoisy type; };
 
 // Item `chunk` of a persistent call -> its first tick within the call and its length (the schedule pve_step_many lays out:
 // n_full items of n_ticks ticks, then the taper).  Shared by the kernel's dequeue (q_take) and the test emulator, which runs

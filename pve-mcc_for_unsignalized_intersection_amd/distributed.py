@@ -15,6 +15,12 @@ def shard_range(n_total, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
+def set_shard_exploration(batch, sigma, seed, n_total, rank, world):
+    """Exploration noise (BatchedIntersections.set_exploration) for the shard `rank` holds of n_total environments: its
+    env_offset is the shard's first global env index, so the ranks together draw what one batch of n_total envs draws."""
+    batch.set_exploration(sigma, seed, env_offset=shard_range(n_total, rank, world)[0])
+
+
 def metrics_vector(metrics, device, extra=()):
     return torch.tensor([metrics[k] for k in _capi.METRIC_NAMES] + [float(x) for x in extra], dtype=torch.float64,
                         device=device)

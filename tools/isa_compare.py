@@ -58,6 +58,10 @@ if __name__ == "__main__":
     with tempfile.TemporaryDirectory() as tmp:
         ko, kn = kernels(disassemble(a.old, tmp)), kernels(disassemble(a.new, tmp))
     dm = demangle(sorted(set(ko) | set(kn)))
+    # kernels are paired by their demangled name without the parameter list: a change of a parameter TYPE (another mangled
+    # symbol for the same template instantiation) is not a removed and a new kernel
+    ko, kn = {dm[k]: v for k, v in ko.items()}, {dm[k]: v for k, v in kn.items()}
+    dm = {k: k for k in set(ko) | set(kn)}
     same = [k for k in ko if k in kn and ko[k] == kn[k]]
     diff = [k for k in ko if k in kn and ko[k] != kn[k]]
     for k in diff:
