@@ -228,6 +228,40 @@ int pve_step_all_actor(pve_handle h, const float *weights, const void *obs_in, d
  * PVE_ERR_INVALID; sigma > 0 on a backend without the noisy actor kernels: PVE_ERR_INVALID. */
 int pve_set_action_noise(pve_handle h, double sigma, uint64_t seed, int64_t env_offset);
 
+/* Target networks on the device: the critic (reference model_agent_maddpg.py:52-74 `critic_network`) and the bootstrap term of
+ * the n-step target (main.py:253-260), for any number of rows per call.  Purely additive to ABI 9: three new symbols, no struct
+ * changes, PVE_ABI_VERSION stays 9; a binding detects an older library by the missing symbols.
+ *
+ * pve_set_target_networks installs a TARGET actor (`agent1_targetactor/...`, layout of pve_set_actor) and / or a critic
+ * (`agent1_target_critic/...` for the bootstrap, `agent1_critic/...` for the online Q): DEVICE float32 vectors, copied into the
+ * handle's workspace flat and packed like pve_set_actor does.  Either pointer may be NULL (that image is kept); both NULL is
+ * PVE_ERR_INVALID.  Independent of pve_set_actor: installing target networks never changes what the acting policy computes.
+ * Critic weight order (TF variable layouts): LayerNorm{gamma[28],beta[28]}, dense{kernel[28][64],bias[64]},
+ * LayerNorm_1{gamma,beta}[64], dense_1{kernel[71][64],bias[64]} (rows 0..63 hidden, 64 own action, 65..70 the six other actions:
+ * model_agent_maddpg.py:66, :82), LayerNorm_2{gamma,beta}[64], dense_2{kernel[64],bias[1]}.
+ *
+ * pve_critic_forward (main.py:76 `agent.Q(state, action, other_action)`): for each of the n rows
+ *   q[i] = dense_2(relu(LN_2(dense_1([relu(LN_1(dense(LN(rows[i])))), act7[i]]))))      act7[i] = own action, six other actions.
+ * pve_bootstrap_q (main.py:253-260): a_k = target_actor(state[i][k]) for ALL seven rows k = 0..6 (the all-zero rows of absent
+ * neighbours included, as main.py:254-255 does), q[i] = critic(state[i][0], a_0, a_1 .. a_6); act7_out (optional) receives the
+ * seven actions.  With `flags` (the pve_outputs.flags block that belongs to the rows) only rows with PVE_F_CTL set and PVE_F_DONE
+ * clear are evaluated (main.py:250-251: no bootstrap behind Done; uncontrolled slots have no transition); every other row gets
+ * q = 0 and act7_out = 0.  flags = NULL evaluates every row.
+ * rows / state have the handle's observation element type (float64, or float32 with PVE_CFG_OBS_F32) and are cast to float32
+ * on load, as the graph's placeholders do.  n is any positive count, not tied to n_envs * capacity: one tick's state_pre and
+ * flags blocks, or a whole [n_ticks][n_envs][cap] trajectory in one call.  Both calls are asynchronous on the handle's stream
+ * and need no pve_reset.  The target networks always run in the split-half matrix-core form (three v_mfma_f32_32x32x16_f16
+ * per block, float32 accumulation), with or without PVE_CFG_ACTOR_F32.
+ * Errors: null or non-positive arguments PVE_ERR_INVALID; networks not installed PVE_ERR_STATE; a backend without the
+ * kernels PVE_ERR_INVALID. */
+#define PVE_CRITIC_N_WEIGHTS 6841
+int pve_set_target_networks(pve_handle h, const float *target_actor /* PVE_ACTOR_N_WEIGHTS */,
+                            const float *critic /* PVE_CRITIC_N_WEIGHTS */);
+int pve_critic_forward(pve_handle h, const void *rows /* [n][28] */, const float *act7 /* [n][7] */,
+                       float *q /* [n] */, int64_t n);
+int pve_bootstrap_q(pve_handle h, const void *state /* [n][7][28] */, const int32_t *flags /* [n] or NULL */,
+                    float *q /* [n] */, float *act7_out /* [n][7] or NULL */, int64_t n);
+
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly
  * pve_step_all() with

@@ -22,6 +22,7 @@ PVE_NBR = 6
 PVE_N_METRICS = 12
 PVE_ENV_OUT_N = 8
 PVE_ACTOR_N_WEIGHTS = 6393
+PVE_CRITIC_N_WEIGHTS = 6841
 ABI_VERSION = 9
 SRC_ZERO, SRC_POOL, SRC_ACTOR, SRC_TABLE = 0, 1, 2, 3
 
@@ -76,7 +77,8 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_scene_update", "pve_compact", "pve_read_env", "pve_read_vehicles", "pve_get_metrics",
            "pve_state_field", "pve_synchronize", "pve_debug_phase_cycles", "pve_actor_forward",
            "pve_step_all_actor", "pve_debug_traffic_probe", "pve_set_intentions", "pve_step_many", "pve_set_actor",
-           "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise")
+           "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise",
+           "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q")
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -109,6 +111,9 @@ def _declare(L):
     L.pve_set_actor.argtypes = [vp, vp]
     L.pve_actor_forward.argtypes = [vp, vp, vp, vp]
     L.pve_set_action_noise.argtypes = [vp, C.c_double, C.c_uint64, C.c_int64]
+    L.pve_set_target_networks.argtypes = [vp, vp, vp]
+    L.pve_critic_forward.argtypes = [vp, vp, vp, vp, C.c_int64]
+    L.pve_bootstrap_q.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
     for name in EXPORTS:
@@ -130,7 +135,11 @@ def load_library(path=None):
     if not os.path.isfile(p):
         raise PveError("%s not found: build the HIP library first (python -c 'import __graft_entry__ as g; "
                        "g.build()' or make -C %s/csrc). There is no CPU fallback." % (p, _HERE))
-    L = _declare(C.CDLL(p))
+    dll = C.CDLL(p)
+    missing = [n for n in EXPORTS if not hasattr(dll, n)]
+    if missing:       # (the target-network entry points were added within ABI 9: an older build lacks the symbols)
+        raise PveError("%s is an older build: it lacks %s (rebuild it)" % (p, ", ".join(missing)))
+    L = _declare(dll)
     if L.pve_abi_version() != ABI_VERSION:
         raise PveError("ABI mismatch: library %d, binding %d" % (L.pve_abi_version(), ABI_VERSION))
     if path is None:

@@ -276,6 +276,91 @@ class BatchedIntersections:
               "pve_set_action_noise")
         self.exploration = (float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset))
 
+    # ------------------------------------------------------------------ target networks: critic and bootstrap Q
+    def set_target_networks(self, actor=None, critic=None):
+        """Install the TARGET actor and / or a critic on the device (pve_set_target_networks); None keeps what is installed.
+        actor: flat float32[6393] or a dict as for set_actor; critic: flat float32[6841] or a dict with the same keys (w2 is
+        dense_1/kernel [71][64]: 64 hidden rows, own action, six other actions -- critic.flat_critic_weights).  Independent of
+        set_actor: the acting policy is untouched."""
+        from .critic import flat_critic_weights
+        if actor is None and critic is None:
+            raise PveError("set_target_networks: pass a target actor, a critic or both")
+        ptr = []
+        with self._own_stream():
+            for w, n, what in ((actor, _capi.PVE_ACTOR_N_WEIGHTS, "target actor"), (critic, _capi.PVE_CRITIC_N_WEIGHTS, "critic")):
+                if w is None:
+                    ptr.append(None)
+                    continue
+                if isinstance(w, dict):
+                    w = flat_critic_weights(w) if what == "critic" else \
+                        np.concatenate([np.asarray(w[k], np.float32).ravel() for k in self.ACTOR_KEYS])
+                t = torch.as_tensor(w, dtype=torch.float32).contiguous()
+                if t.numel() != n:
+                    raise PveError("%s needs %d float32 weights, got %d" % (what, n, t.numel()))
+                ptr.append(t.to(self.device))
+            self._bind_stream()
+            check(self.lib, self.lib.pve_set_target_networks(self._h, *[C.c_void_p(t.data_ptr() if t is not None else 0) for t in ptr]),
+                  "pve_set_target_networks")
+            self._target_w = [t if t is not None else old for t, old in zip(ptr, getattr(self, "_target_w", [None, None]))]
+
+    def _rows_arg(self, x, tail, what):
+        """A contiguous device tensor of the handle's observation type whose trailing dimensions are `tail` -> (tensor, rows)"""
+        if not torch.is_tensor(x):
+            x = torch.as_tensor(np.asarray(x))
+        x = x.to(device=self.device, dtype=self.obs_dtype).contiguous()
+        if tuple(x.shape[-len(tail):]) != tail or x.numel() == 0:
+            raise PveError("%s must be [..., %s] and not empty" % (what, ", ".join(str(t) for t in tail)))
+        return x, x.numel() // int(np.prod(tail))
+
+    def _f32_out(self, out, shape, what):
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != int(np.prod(shape)) or out.device.type != self.device.type:
+            raise PveError("%s must be a contiguous float32 device tensor of %d elements" % (what, int(np.prod(shape))))
+        return out
+
+    def critic_q(self, rows, act7, out=None):
+        """Q of the installed critic (main.py:76 `agent.Q(state, action, other_action)`): rows [..., 28] (the handle's
+        observation type), act7 [..., 7] float32 (own action, then the six other actions) -> float32 [...] (device tensor)."""
+        with self._own_stream():
+            rows, n = self._rows_arg(rows, (28,), "rows")
+            a = (act7 if torch.is_tensor(act7) else torch.as_tensor(np.asarray(act7))).to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(a.shape) != tuple(rows.shape[:-1]) + (7,):
+                raise PveError("act7 must be [..., 7] with the leading shape of rows")
+            q = self._f32_out(out, tuple(rows.shape[:-1]), "out")
+            self._bind_stream()
+            check(self.lib, self.lib.pve_critic_forward(self._h, C.c_void_p(rows.data_ptr()), C.c_void_p(a.data_ptr()),
+                                                        C.c_void_p(q.data_ptr()), n), "pve_critic_forward")
+        return q
+
+    def bootstrap_q(self, state=None, flags=None, out=None, actions_out=None):
+        """The bootstrap term of the n-step target (main.py:253-260) with the installed target networks: every one of the 7
+        rows of `state` [..., 7, 28] through the target actor, then the target critic on row 0 with those 7 actions.
+        flags [...] int32 (the tick's `flags` output): only rows with F_CTL set and F_DONE clear are evaluated, the others
+        get 0.  state=None: the batch's own state_pre / flags -- the trajectory blocks of the last
+        step_many(trajectory=True) when there was one, else the single-tick views.  Returns (q float32 [...], act7 float32
+        [..., 7]) device tensors (`out` / `actions_out` when given)."""
+        with self._own_stream():
+            if state is None:
+                last = getattr(self, "_last_traj", None)
+                src = last[1] if last is not None and last[0] == self.ticks else self.out     # (stale once the batch stepped on)
+                if "state_pre" not in src or "flags" not in src:
+                    raise PveError("bootstrap_q(): the batch was created without the state_pre / flags outputs; pass state")
+                state, flags = src["state_pre"], (src["flags"] if flags is None else flags)
+            state, n = self._rows_arg(state, (7, 28), "state")
+            lead = tuple(state.shape[:-2])
+            if flags is not None:
+                flags = (flags if torch.is_tensor(flags) else torch.as_tensor(np.asarray(flags))).to(device=self.device, dtype=torch.int32).contiguous()
+                if tuple(flags.shape) != lead:
+                    raise PveError("flags must have the leading shape of state")
+            q = self._f32_out(out, lead, "out")
+            a7 = self._f32_out(actions_out, lead + (7,), "actions_out")
+            self._bind_stream()
+            check(self.lib, self.lib.pve_bootstrap_q(self._h, C.c_void_p(state.data_ptr()),
+                                                     C.c_void_p(flags.data_ptr() if flags is not None else 0),
+                                                     C.c_void_p(q.data_ptr()), C.c_void_p(a7.data_ptr()), n), "pve_bootstrap_q")
+        return q, a7
+
     def act(self):
         """actions [n_envs, capacity] = actor(obs) for the controlled slots (+ the exploration noise, set_exploration),
         0 elsewhere (device tensor)."""
@@ -414,6 +499,8 @@ class BatchedIntersections:
                     self._obs[self._obs_cur].copy_(traj["obs_post"][n_ticks - 1])
                 for n, tns in self.out.items():
                     tns.copy_(traj[n][n_ticks - 1])
+        # (what bootstrap_q() reads by default: the blocks this call filled)
+        self._last_traj = (self.ticks, {n: tns[:n_ticks] for n, tns in traj.items()}) if n_ticks > 0 else None
         return traj
 
     def prepare_step_many(self, n_ticks, source=None, chunk=0, persistent=False):
@@ -601,6 +688,23 @@ class PipelinedIntersections:
         for k, sub in enumerate(self.subs):
             with self._on(k):
                 sub.set_actor(weights)
+
+    def set_target_networks(self, actor=None, critic=None):
+        for k, sub in enumerate(self.subs):
+            with self._on(k):
+                sub.set_target_networks(actor, critic)
+
+    def critic_q(self, rows, act7, out=None):
+        """BatchedIntersections.critic_q per sub-batch: rows / act7 (/ out) as lists of per-sub-batch tensors, or tensors
+        whose first dimension is the environment (cut at `bounds`).  Returns the list of per-sub-batch results."""
+        return [sub.critic_q(r, a, out=o) for sub, r, a, o in zip(self.subs, self._parts(rows), self._parts(act7), self._parts(out))]
+
+    def bootstrap_q(self, state=None, flags=None, out=None, actions_out=None):
+        """BatchedIntersections.bootstrap_q per sub-batch (each on its own stream; state=None: every sub-batch's own
+        state_pre / flags).  Explicit arguments: lists of per-sub-batch tensors, or tensors whose first dimension is the
+        environment.  Returns the list of per-sub-batch (q, act7) pairs."""
+        return [sub.bootstrap_q(s, f, out=o, actions_out=a)
+                for sub, s, f, o, a in zip(self.subs, self._parts(state), self._parts(flags), self._parts(out), self._parts(actions_out))]
 
     def set_exploration(self, sigma, seed=0):
         """BatchedIntersections.set_exploration for every sub-batch, each with the global index of its first environment:

@@ -31,6 +31,15 @@
 //                                           const pve::ActionNoise &, int cap, void *stream, std::string &err);
 //                                                // optional, all three or none: launch_actor / launch_rollout / launch_rollout_geo +
 //                                                // the exploration noise of pve_set_action_noise (ActionNoise::tick0 = first tick)
+//     static int   pack_target_networks(const float *actor_w, float *actor_flat, unsigned char *actor_packed, const float *critic_w,
+//                                       float *critic_flat, unsigned char *critic_packed, void *stream, std::string &err);
+//     static int   launch_critic(const unsigned char *critic_packed, const void *rows, int obs_f32, const float *act7, float *q,
+//                                long long n, void *stream, std::string &err);
+//     static int   launch_bootstrap_q(const unsigned char *actor_packed, const unsigned char *critic_packed, const void *state,
+//                                     int obs_f32, const int32_t *flags, float *q, float *act7_out, long long n, void *stream,
+//                                     std::string &err);
+//                                                // optional, all three or none: pve_set_target_networks / pve_critic_forward /
+//                                                // pve_bootstrap_q (a NULL weight pointer of pack_target_networks = keep that image)
 //   };
 //
 // pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
@@ -185,6 +194,28 @@ template <class B> struct backend_noise<B, decltype((void)&B::launch_actor_noisy
         return B::launch_rollout_geo_noisy(g, P, R, nz, cap, stream, err);
     }
 };
+// The target networks (pve_set_target_networks / pve_critic_forward / pve_bootstrap_q) need the kernels of pve_critic.h:
+// Backend::pack_target_networks / launch_critic / launch_bootstrap_q (detected by the last).  A backend without them exports the
+// three entry points all the same; they validate their arguments and then refuse with PVE_ERR_INVALID.
+template <class B, class = void> struct backend_target_q {
+    static constexpr bool value = false;
+    static int pack(const float *, float *, unsigned char *, const float *, float *, unsigned char *, void *, std::string &) { return -1; }
+    static int critic(const unsigned char *, const void *, int, const float *, float *, long long, void *, std::string &) { return -1; }
+    static int bootstrap(const unsigned char *, const unsigned char *, const void *, int, const int32_t *, float *, float *, long long,
+                         void *, std::string &) { return -1; }
+};
+template <class B> struct backend_target_q<B, decltype((void)&B::launch_bootstrap_q)> {
+    static constexpr bool value = true;
+    static int pack(const float *aw, float *af, unsigned char *ap, const float *cw, float *cf, unsigned char *cp, void *stream,
+                    std::string &err) { return B::pack_target_networks(aw, af, ap, cw, cf, cp, stream, err); }
+    static int critic(const unsigned char *cp, const void *rows, int obs_f32, const float *act7, float *q, long long n, void *stream,
+                      std::string &err) { return B::launch_critic(cp, rows, obs_f32, act7, q, n, stream, err); }
+    static int bootstrap(const unsigned char *ap, const unsigned char *cp, const void *state, int obs_f32, const int32_t *flags, float *q,
+                         float *act7_out, long long n, void *stream, std::string &err)
+    {
+        return B::launch_bootstrap_q(ap, cp, state, obs_f32, flags, q, act7_out, n, stream, err);
+    }
+};
 extern "C" {
 
 int pve_abi_version(void) { return PVE_ABI_VERSION; }
@@ -245,6 +276,7 @@ int pve_create(const pve_config *cfg, int n_envs, int capacity, int device_id, v
     h->has_arrivals = false; h->is_reset = false; h->ticks_since_reset = 0;
     h->phase_cycles = nullptr;
     h->has_actor = false;
+    h->has_tactor = false; h->has_critic = false;
     h->q_done_base = 0;
     h->last_launch_kind = PVE_LAUNCH_NONE;
     h->stop_phase = -1;
@@ -425,6 +457,56 @@ int pve_actor_forward(pve_handle h, const float *weights, const void *obs, doubl
     DevScope dev_scope(h->device);
     std::string err;
     if (run_actor(h, obs, actions, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_actor_forward: " + err);
+    return PVE_OK;
+}
+
+static int no_target_kernels(const char *who)
+{
+    return fail(PVE_ERR_INVALID, std::string(who) + ": this backend has no critic / bootstrap kernels");
+}
+
+int pve_set_target_networks(pve_handle h, const float *target_actor, const float *critic)
+{
+    if (!h || (!target_actor && !critic)) return fail(PVE_ERR_INVALID, "pve_set_target_networks: null argument (at least one network is needed)");
+    if (!backend_target_q<Backend>::value) return no_target_kernels("pve_set_target_networks");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_target_q<Backend>::pack(target_actor, (float *)(h->ws + h->L.off_tactor_flat), (unsigned char *)(h->ws + h->L.off_tactor_packed),
+                                        critic, (float *)(h->ws + h->L.off_critic_flat), (unsigned char *)(h->ws + h->L.off_critic_packed),
+                                        h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_set_target_networks: " + err);
+    if (target_actor) h->has_tactor = true;
+    if (critic) h->has_critic = true;
+    return PVE_OK;
+}
+
+int pve_critic_forward(pve_handle h, const void *rows, const float *act7, float *q, int64_t n)
+{
+    if (!h || !rows || !act7 || !q) return fail(PVE_ERR_INVALID, "pve_critic_forward: null argument");
+    if (n <= 0) return fail(PVE_ERR_INVALID, "pve_critic_forward: n must be > 0");
+    if (!backend_target_q<Backend>::value) return no_target_kernels("pve_critic_forward");
+    if (!h->has_critic) return fail(PVE_ERR_STATE, "pve_critic_forward: no critic installed (pve_set_target_networks)");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_target_q<Backend>::critic((const unsigned char *)(h->ws + h->L.off_critic_packed), rows, actor_mode(h) & 1, act7, q,
+                                          (long long)n, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_critic_forward: " + err);
+    return PVE_OK;
+}
+
+int pve_bootstrap_q(pve_handle h, const void *state, const int32_t *flags, float *q, float *act7_out, int64_t n)
+{
+    if (!h || !state || !q) return fail(PVE_ERR_INVALID, "pve_bootstrap_q: null argument");
+    if (n <= 0) return fail(PVE_ERR_INVALID, "pve_bootstrap_q: n must be > 0");
+    if (!backend_target_q<Backend>::value) return no_target_kernels("pve_bootstrap_q");
+    if (!h->has_tactor || !h->has_critic)
+        return fail(PVE_ERR_STATE, "pve_bootstrap_q: needs a target actor and a critic (pve_set_target_networks)");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_target_q<Backend>::bootstrap((const unsigned char *)(h->ws + h->L.off_tactor_packed),
+                                             (const unsigned char *)(h->ws + h->L.off_critic_packed), state, actor_mode(h) & 1, flags, q,
+                                             act7_out, (long long)n, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_bootstrap_q: " + err);
     return PVE_OK;
 }
 

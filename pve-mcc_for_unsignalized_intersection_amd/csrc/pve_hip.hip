@@ -18,6 +18,7 @@
 #include "pve_tick_core.h"
 #include "pve_tick_geo.h"
 #include "pve_actor.h"
+#include "pve_critic.h"
 
 using namespace pve;
 
@@ -1358,6 +1359,48 @@ struct Backend {
         if (cap != 64 && cap != 128 && cap != 256) return bad_cap(cap, err);
         if (mode & 1) launch_actor_t<float>(W, packed, (const float *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, ids, nz, s);
         else launch_actor_t<double>(W, packed, (const double *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, ids, nz, s);
+        return check_launch(err);
+    }
+    // pve_set_target_networks: the target actor through the actor's own packing kernel, the critic through k_critic_pack
+    static int pack_target_networks(const float *actor_w, float *actor_flat, unsigned char *actor_packed, const float *critic_w,
+                                    float *critic_flat, unsigned char *critic_packed, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        if (actor_w) {
+            hipError_t e = hipMemcpyAsync(actor_flat, actor_w, sizeof(float) * AW_TOTAL, hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) { err = hip_err("hipMemcpyAsync", e); return -1; }
+            hipLaunchKernelGGL(k_actor_pack, dim3(1), dim3(256), 0, s, actor_w, actor_packed);
+        }
+        if (critic_w) {
+            hipError_t e = hipMemcpyAsync(critic_flat, critic_w, sizeof(float) * CW_TOTAL, hipMemcpyDeviceToDevice, s);
+            if (e != hipSuccess) { err = hip_err("hipMemcpyAsync", e); return -1; }
+            hipLaunchKernelGGL(k_critic_pack, dim3(1), dim3(256), 0, s, critic_w, critic_packed);
+        }
+        return check_launch(err);
+    }
+    // persistent workgroups of 4 waves, every wave walks chunks of 64 rows: as many workgroups as stay resident (LDS: the
+    // bootstrap kernel holds both packed networks, 2 per CU; the critic alone 4 per CU), never more than there are chunks
+    static int target_q_grid(long long n, int per_cu)
+    {
+        const long long want = (n + 255) / 256, cap = 256LL * per_cu;
+        return (int)(want < cap ? want : cap);
+    }
+    static int launch_critic(const unsigned char *critic_packed, const void *rows, int obs_f32, const float *act7, float *q,
+                             long long n, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int grid = target_q_grid(n, 4);
+        if (obs_f32) hipLaunchKernelGGL((k_target_q<float, false>), dim3(grid), dim3(256), 0, s, nullptr, critic_packed, (const float *)rows, act7, nullptr, q, nullptr, n);
+        else hipLaunchKernelGGL((k_target_q<double, false>), dim3(grid), dim3(256), 0, s, nullptr, critic_packed, (const double *)rows, act7, nullptr, q, nullptr, n);
+        return check_launch(err);
+    }
+    static int launch_bootstrap_q(const unsigned char *actor_packed, const unsigned char *critic_packed, const void *state, int obs_f32,
+                                  const int32_t *flags, float *q, float *act7_out, long long n, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int grid = target_q_grid(n, 2);
+        if (obs_f32) hipLaunchKernelGGL((k_target_q<float, true>), dim3(grid), dim3(256), 0, s, actor_packed, critic_packed, (const float *)state, nullptr, flags, q, act7_out, n);
+        else hipLaunchKernelGGL((k_target_q<double, true>), dim3(grid), dim3(256), 0, s, actor_packed, critic_packed, (const double *)state, nullptr, flags, q, act7_out, n);
         return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)

@@ -235,5 +235,6 @@ struct pve_handle_s {
     int stop_phase;                   // pve_debug_stop_phase (diagnostics), -1 = off
     unsigned q_done_base;             // persistent roll-out: items completed per intersection since pve_reset (cumulative)
     int last_launch_kind;             // PVE_LAUNCH_*: what the last stepping call launched (pve_debug_last_launch)
+    bool has_tactor, has_critic;      // pve_set_target_networks installed a target actor / a critic in the workspace
     pve::ActionNoise noise;           // pve_set_action_noise (sigma = 0: off); tick0 is filled in per launch
 };

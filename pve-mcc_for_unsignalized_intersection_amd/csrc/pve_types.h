@@ -209,9 +209,13 @@ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // pve_set_actor keeps two images of the actor in the handle's workspace: the flat float32 weights (the exact float32
 // kernel k_actor_t reads them) and the packed split-half form (pve_actor.h: AP_BYTES_PADDED)
 constexpr size_t ACTOR_FLAT_BYTES = 25600, ACTOR_PACKED_BYTES = 26880;
+// pve_set_target_networks keeps the same two images of a TARGET actor, and of a critic (pve_critic.h: 6841 weights,
+// CP_BYTES_PADDED), behind everything else in the workspace (the offsets of the other blocks are what they were)
+constexpr size_t CRITIC_FLAT_BYTES = 27392, CRITIC_PACKED_BYTES = 30976;
 
 struct Layout {
-    size_t off_headers, off_f64[NF64], off_i32[NI32], off_actor_flat, off_actor_packed, off_queue, total;
+    size_t off_headers, off_f64[NF64], off_i32[NI32], off_actor_flat, off_actor_packed, off_queue, off_tactor_flat, off_tactor_packed,
+           off_critic_flat, off_critic_packed, total;
 };
 
 inline Layout make_layout(int n_envs, int cap)
@@ -224,6 +228,10 @@ inline Layout make_layout(int n_envs, int cap)
     L.off_actor_flat = o; o = align_up(o + ACTOR_FLAT_BYTES, 256);
     L.off_actor_packed = o; o = align_up(o + ACTOR_PACKED_BYTES, 256);
     L.off_queue = o; o = align_up(o + sizeof(RolloutQueue) + 4 * (size_t)n_envs, 256);
+    L.off_tactor_flat = o; o = align_up(o + ACTOR_FLAT_BYTES, 256);
+    L.off_tactor_packed = o; o = align_up(o + ACTOR_PACKED_BYTES, 256);
+    L.off_critic_flat = o; o = align_up(o + CRITIC_FLAT_BYTES, 256);
+    L.off_critic_packed = o; o = align_up(o + CRITIC_PACKED_BYTES, 256);
     L.total = o;
     return L;
 }
