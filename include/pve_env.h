@@ -262,6 +262,76 @@ int pve_critic_forward(pve_handle h, const void *rows /* [n][28] */, const float
 int pve_bootstrap_q(pve_handle h, const void *state /* [n][7][28] */, const int32_t *flags /* [n] or NULL */,
                     float *q /* [n] */, float *act7_out /* [n][7] or NULL */, int64_t n);
 
+/* N-STEP TRANSITIONS from retained trajectory blocks (reference main.py:243-266).  Additive within ABI 9: two new symbols and two
+ * new structs, nothing existing changes; a binding detects an older library by the missing symbols.
+ *
+ * The reference keeps, per controlled vehicle, a sliding buffer of its last seq_max_step + 1 = 13 ticks.  When the buffer is
+ * full or the vehicle is Done it folds the rewards into  r = r_last (+ gamma * Q'(state_next_last) unless Done),
+ * r = r_k + gamma * r  backwards through the older entries, and puts ONE transition -- (s0, a, r) of the OLDEST entry -- into
+ * the replay buffer.  The learner reads row 0 of s0 (28 numbers, main.py:74), the 7 actions and the target: 36 float32.
+ *
+ * This is a STATELESS pass over the blocks pve_step_many(trajectory = 1) filled; the handle only supplies n_envs, capacity, the
+ * observation element type (PVE_CFG_OBS_F32) and the stream.  It is indexed by a window's START (tick u, env, slot) with
+ * PVE_F_CTL set at u and follows the vehicle through new_slot, at most window - 1 links.  A start emits
+ *   - a FULL window (`window` entries collected): bootstrapped with q_boot at the closing entry unless that entry is Done;
+ *   - a window closed by PVE_F_DONE before it is full ONLY when u is the vehicle's first controlled tick, i.e. its s0 row is all
+ *     zero (pve_outputs.obs_post: only a vehicle spawned at the end of the previous tick has one): at Done the reference emits
+ *     the oldest buffered entry and drops the younger ones.  mode & PVE_NSTEP_TAIL emits those truncated windows too (the
+ *     usual n-step treatment of episode ends);
+ *   - nothing when the walk meets a slot without PVE_F_CTL or a -1 link before it closes.
+ * Slot-indexed: for lane_num 4 / 8 the reference's `ids` order differs from slot order, which does not matter here.
+ *
+ * Two segments: `prev` (n_ticks = 0, or >= window; only its last `window` ticks are read) and `cur`, consecutive in time.  A
+ * start emits in this call IFF ITS WINDOW CLOSES AT A TICK OF `cur`: starts of `cur` whose walk runs off the end are pending and
+ * emit in the next call, when `cur` is passed as `prev`; with prev.n_ticks = 0 the windows that were open before `cur` are lost.
+ * Fields of an emitted record: the s0 row = the row the actor consumed at u = obs_post of tick u - 1 at the slot (`obs_first`
+ * for the first tick of `cur` when there is no `prev`); the 7 actions = column 2 of the 7 rows of state_pre at u (ref :290);
+ * the target in float64: Q' = the float32 of q_boot (pve_bootstrap_q on cur's state_pre / flags) widened to double, then
+ * gamma * Q' and every Horner step as separately rounded IEEE operations (no fused multiply-add) -- csrc/pve_nstep.h, bit-equal to
+ * pve_mcc_amd/nstep.py.  (The type of the reference's own gamma * Q depends on the NumPy version; this library defines float64.)
+ *
+ * pve_nstep_scan fills, for the n_cand = min(prev.n_ticks, window - 1) + cur.n_ticks candidate start ticks (tick index relative
+ * to cur: -min(..) .. cur.n_ticks - 1), the dense start-indexed `target` (float64) and `code` (int32: entries used in bits 0-7,
+ * bit 8 bootstrapped, bit 9 closed by Done; 0 = no transition) [n_cand][n_envs][cap], `offsets` = the index of the first record
+ * of every group of 64 slots (int32 [n_cand * n_envs * cap / 64 + 1], the last entry = the count) and `total` (int64, DEVICE).
+ * Record order: (tick, env, slot) ascending, whatever the launch geometry (ballot + popcount per wave, no atomics).
+ * pve_nstep_gather (same struct, after the scan, same stream) writes the first max_records records in that order:
+ * records float32 [max_records][36] = s0 row [28], actions [7], target [1] (cast from the handle's observation type / float64),
+ * index int32 [max_records][4] = tick relative to cur (negative: a start in prev), env, slot, code.  `total` always holds the
+ * true count.  obs_post / obs_first / records / index must be 16-byte aligned.
+ * Errors (PVE_ERR_INVALID): null required pointers, window outside 1 .. 16, gamma NaN or outside [0, 1], 0 < prev.n_ticks <
+ * window, cur.n_ticks < 1, max_records < 0, more than 2^31 - 1 candidate slots, a misaligned buffer, a backend without the
+ * kernels.  Both calls are asynchronous on the handle's stream and need no pve_reset. */
+#define PVE_NSTEP_TAIL 0x1
+#define PVE_NSTEP_MAX_WINDOW 16
+#define PVE_NSTEP_RECORD 36
+typedef struct pve_nstep_segment {
+    int32_t n_ticks;
+    const void *obs_post;         /* [n_ticks][n_envs][cap][28]   float64, or float32 with PVE_CFG_OBS_F32 */
+    const void *state_pre;        /* [n_ticks][n_envs][cap][7][28] same element type */
+    const double *reward;         /* [n_ticks][n_envs][cap] */
+    const int32_t *flags;         /* [n_ticks][n_envs][cap] */
+    const int32_t *new_slot;      /* [n_ticks][n_envs][cap] */
+} pve_nstep_segment;
+typedef struct pve_nstep {
+    double gamma;                 /* main.py:227: tanh((epoch + 6) / 12) * 0.9 */
+    int32_t window;               /* seq_max_step + 1 = 13 in the reference */
+    int32_t mode;                 /* PVE_NSTEP_* */
+    pve_nstep_segment prev, cur;
+    const void *obs_first;        /* [n_envs][cap][28]: the rows stored before cur's first tick; read when prev.n_ticks = 0 */
+    const float *q_boot;          /* [cur.n_ticks][n_envs][cap] (pve_bootstrap_q) */
+    double *target;               /* scan out / gather in */
+    int32_t *code;
+    int32_t *offsets;
+    int64_t *total;
+    int64_t max_records;          /* gather */
+    float *records;
+    int32_t *index;
+    int32_t block_threads;        /* 0 = default; diagnostics: threads per workgroup of the scan (a multiple of 64, <= 1024) */
+} pve_nstep;
+int pve_nstep_scan(pve_handle h, const pve_nstep *ns);
+int pve_nstep_gather(pve_handle h, const pve_nstep *ns);
+
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly
  * pve_step_all() with

@@ -23,6 +23,7 @@ PVE_N_METRICS = 12
 PVE_ENV_OUT_N = 8
 PVE_ACTOR_N_WEIGHTS = 6393
 PVE_CRITIC_N_WEIGHTS = 6841
+NSTEP_TAIL, NSTEP_MAX_WINDOW, NSTEP_RECORD = 0x1, 16, 36
 ABI_VERSION = 9
 SRC_ZERO, SRC_POOL, SRC_ACTOR, SRC_TABLE = 0, 1, 2, 3
 
@@ -57,6 +58,18 @@ class PveRollout(C.Structure):
                 ("persistent", C.c_int32)]
 
 
+class PveNstepSegment(C.Structure):
+    _fields_ = [("n_ticks", C.c_int32), ("obs_post", C.c_void_p), ("state_pre", C.c_void_p), ("reward", C.c_void_p),
+                ("flags", C.c_void_p), ("new_slot", C.c_void_p)]
+
+
+class PveNstep(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("window", C.c_int32), ("mode", C.c_int32), ("prev", PveNstepSegment),
+                ("cur", PveNstepSegment), ("obs_first", C.c_void_p), ("q_boot", C.c_void_p), ("target", C.c_void_p),
+                ("code", C.c_void_p), ("offsets", C.c_void_p), ("total", C.c_void_p), ("max_records", C.c_int64),
+                ("records", C.c_void_p), ("index", C.c_void_p), ("block_threads", C.c_int32)]
+
+
 class PveVehicle(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("p", "v", "a", "jerk", "jerk_sum", "vir_dis", "closer_p")] + \
                [(n, C.c_int32) for n in ("lane", "j", "id", "vnum", "seq_in_lane", "control", "finish", "done",
@@ -78,7 +91,7 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_state_field", "pve_synchronize", "pve_debug_phase_cycles", "pve_actor_forward",
            "pve_step_all_actor", "pve_debug_traffic_probe", "pve_set_intentions", "pve_step_many", "pve_set_actor",
            "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise",
-           "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q")
+           "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather")
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -114,6 +127,8 @@ def _declare(L):
     L.pve_set_target_networks.argtypes = [vp, vp, vp]
     L.pve_critic_forward.argtypes = [vp, vp, vp, vp, C.c_int64]
     L.pve_bootstrap_q.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
+    L.pve_nstep_scan.argtypes = [vp, C.POINTER(PveNstep)]
+    L.pve_nstep_gather.argtypes = [vp, C.POINTER(PveNstep)]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
     for name in EXPORTS:

@@ -361,6 +361,104 @@ class BatchedIntersections:
                                                      C.c_void_p(q.data_ptr()), C.c_void_p(a7.data_ptr()), n), "pve_bootstrap_q")
         return q, a7
 
+    # ------------------------------------------------------------------ n-step transitions (pve_nstep_scan / pve_nstep_gather)
+    _NSTEP_KEYS = ("obs_post", "state_pre", "reward", "flags", "new_slot")
+
+    def _nstep_segment(self, seg, blocks, what):
+        for k in self._NSTEP_KEYS:
+            if k not in blocks:
+                raise PveError("nstep_transitions: %s lacks the %s output (create the batch with state_pre, reward, flags, new_slot)" % (what, k))
+        n = int(blocks["flags"].shape[0])
+        want = dict(obs_post=((n, self.n_envs, self.capacity, 28), self.obs_dtype), state_pre=((n, self.n_envs, self.capacity, 7, 28), self.obs_dtype),
+                    reward=((n, self.n_envs, self.capacity), torch.float64), flags=((n, self.n_envs, self.capacity), torch.int32),
+                    new_slot=((n, self.n_envs, self.capacity), torch.int32))
+        keep = []
+        for k in self._NSTEP_KEYS:
+            tns = blocks[k]
+            if tuple(tns.shape) != want[k][0] or tns.dtype != want[k][1] or tns.device.type != self.device.type:
+                raise PveError("nstep_transitions: %s[%r] must be a %s device tensor of shape %s" % (what, k, want[k][1], want[k][0]))
+            tns = tns.contiguous()
+            keep.append(tns)
+            setattr(seg, k, tns.data_ptr())
+        seg.n_ticks = n
+        return n, keep
+
+    def nstep_transitions(self, gamma, window=13, prev=None, q=None, tail=False, max_records=None, cur=None, obs_first=None,
+                          block_threads=0):
+        """The n-step training transitions of a trajectory roll-out, assembled on the device (reference main.py:243-266):
+        for every controlled vehicle and tick the reference's sliding buffer of `window` = seq_max_step + 1 ticks, folded into
+        target = sum_k gamma^k r_k (+ gamma^window Q' behind the last entry unless the vehicle is Done), in float64 and in the
+        reference's backward order (bit-equal to nstep.py).  Returns (records, index, total):
+          records float32 [M, 36]: row 0 of s0 [28] (the row the actor consumed), the 7 actions, the target;
+          index   int32 [M, 4]: start tick relative to cur (negative: in prev), env, slot, code (entries used | 0x100
+                  bootstrapped | 0x200 closed by Done); record order is (tick, env, slot) ascending;
+          total   the number of transitions.
+        cur: the blocks of the trajectory (default: those of the last step_many(trajectory=...), which must be this batch's
+        latest stepping call).  prev: the blocks of the step_many call right before it (the dict it returned), so that windows
+        that cross the two calls emit: a transition is emitted by the call in which its window CLOSES, windows still open at
+        the end of cur emit when cur is passed as prev next time (alternate two alloc_trajectory() buffer sets).  prev=None:
+        the windows that were open before cur are LOST (harmless right after reset()).  prev must hold at least `window`
+        ticks; that the two calls are consecutive is checked against the recorded tick stamps.
+        q: float32 [n_ticks, n_envs, cap] bootstrap Q of cur (default: bootstrap_q() on cur).  tail=True also emits the
+        windows a Done truncates (the reference drops all but the oldest).  max_records=None reads `total` once (one
+        synchronisation) and allocates exactly, M = total; a given max_records allocates that many rows without synchronising,
+        fills the first min(total, max_records) in order and returns `total` as a 0-dim device tensor.
+        lane_num 4 / 8: the pass is slot-indexed; that `ids` order differs from slot order there does not matter."""
+        window = int(window)
+        with self._own_stream():
+            stamped = cur is None
+            if stamped:
+                last = getattr(self, "_last_traj", None)
+                if last is None or last[0] != self.ticks:
+                    raise PveError("nstep_transitions: no trajectory of the latest stepping call (step_many(trajectory=...)); pass cur")
+                cur = last[1]
+                if prev is None and obs_first is None:
+                    obs_first = last[3]
+                if prev is not None:
+                    before = getattr(self, "_prev_traj", None)
+                    if before is None or "flags" not in prev or before[1]["flags"].data_ptr() != prev["flags"].data_ptr() or before[0] != last[2]:
+                        raise PveError("nstep_transitions: prev is not the trajectory of the step_many call right before cur")
+                    prev = before[1]
+            ns = _capi.PveNstep()
+            n_cur, keep = self._nstep_segment(ns.cur, cur, "cur")
+            n_prev = 0
+            if prev is not None:
+                n_prev, keep_prev = self._nstep_segment(ns.prev, prev, "prev")
+                keep += keep_prev
+                if n_prev < window:
+                    raise PveError("nstep_transitions: prev holds %d ticks, fewer than window = %d (pass prev=None and accept the loss)" % (n_prev, window))
+            else:
+                if obs_first is None:
+                    raise PveError("nstep_transitions: without prev, obs_first (the rows stored before cur's first tick) is needed")
+                obs_first, _ = self._rows_arg(obs_first, (self.n_envs, self.capacity, 28), "obs_first")
+                ns.obs_first = obs_first.data_ptr()
+            if q is None:
+                q, _ = self.bootstrap_q(cur["state_pre"], cur["flags"])
+            q = q.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(q.shape) != (n_cur, self.n_envs, self.capacity):
+                raise PveError("nstep_transitions: q must be [n_ticks, n_envs, capacity]")
+            n_cand = min(n_prev, window - 1) + n_cur
+            dev = self.device
+            target = torch.empty(n_cand, self.n_envs, self.capacity, dtype=torch.float64, device=dev)
+            code = torch.empty(n_cand, self.n_envs, self.capacity, dtype=torch.int32, device=dev)
+            offsets = torch.empty(n_cand * self.n_envs * self.capacity // 64 + 1, dtype=torch.int32, device=dev)
+            total = torch.zeros((), dtype=torch.int64, device=dev)
+            ns.gamma, ns.window, ns.mode = float(gamma), window, (_capi.NSTEP_TAIL if tail else 0)
+            ns.q_boot, ns.target, ns.code, ns.offsets, ns.total = q.data_ptr(), target.data_ptr(), code.data_ptr(), offsets.data_ptr(), total.data_ptr()
+            ns.block_threads = int(block_threads)
+            self._bind_stream()
+            check(self.lib, self.lib.pve_nstep_scan(self._h, C.byref(ns)), "pve_nstep_scan")
+            if max_records is None:
+                n_out = total_out = int(total.item())
+            else:
+                n_out, total_out = int(max_records), total
+            records = torch.empty(n_out, _capi.NSTEP_RECORD, dtype=torch.float32, device=dev)
+            index = torch.empty(n_out, 4, dtype=torch.int32, device=dev)
+            ns.max_records, ns.records, ns.index = n_out, records.data_ptr(), index.data_ptr()
+            check(self.lib, self.lib.pve_nstep_gather(self._h, C.byref(ns)), "pve_nstep_gather")
+            self._nstep_last = (target, code, offsets)      # (diagnostics: the dense scan outputs of the last call)
+        return records, index, total_out
+
     def act(self):
         """actions [n_envs, capacity] = actor(obs) for the controlled slots (+ the exploration noise, set_exploration),
         0 elsewhere (device tensor)."""
@@ -494,13 +592,21 @@ class BatchedIntersections:
                     raise PveError("step_many with state_pre reads the handle's observation view: update_views must stay True")
             check(self.lib, self.lib.pve_step_many(self._h, C.byref(ro), C.byref(o)), "pve_step_many")
             self.ticks += n_ticks
+            obs_first = self._obs[self._obs_cur] if self._obs is not None else None   # the rows stored before this call
             if n_ticks > 0 and update_views:     # the handle's single-tick views keep showing the latest tick
                 if self._obs is not None:
+                    if len(self._obs) == 2:      # (into the other buffer of the pair: the rows in front of the call stay readable
+                        self._obs_cur ^= 1       #  for nstep_transitions until the batch steps on, at no cost)
                     self._obs[self._obs_cur].copy_(traj["obs_post"][n_ticks - 1])
                 for n, tns in self.out.items():
                     tns.copy_(traj[n][n_ticks - 1])
-        # (what bootstrap_q() reads by default: the blocks this call filled)
-        self._last_traj = (self.ticks, {n: tns[:n_ticks] for n, tns in traj.items()}) if n_ticks > 0 else None
+        # (what bootstrap_q() / nstep_transitions() read by default: the blocks this call filled, the tick stamps of its end and
+        #  start, the rows stored before it; the call before it is remembered to check that `prev` and `cur` are consecutive)
+        if n_ticks > 0:
+            self._prev_traj = getattr(self, "_last_traj", None)
+            self._last_traj = (self.ticks, {n: tns[:n_ticks] for n, tns in traj.items()}, self.ticks - n_ticks, obs_first)
+        else:
+            self._last_traj = None
         return traj
 
     def prepare_step_many(self, n_ticks, source=None, chunk=0, persistent=False):
@@ -705,6 +811,24 @@ class PipelinedIntersections:
         environment.  Returns the list of per-sub-batch (q, act7) pairs."""
         return [sub.bootstrap_q(s, f, out=o, actions_out=a)
                 for sub, s, f, o, a in zip(self.subs, self._parts(state), self._parts(flags), self._parts(out), self._parts(actions_out))]
+
+    def nstep_transitions(self, gamma, window=13, prev=None, q=None, tail=False, max_records=None):
+        """BatchedIntersections.nstep_transitions per sub-batch (each on its own stream), the pieces concatenated in env order
+        (within a piece: tick, env, slot ascending); the index carries GLOBAL env numbers.  prev / q: None, or lists with one
+        entry per sub-batch (what step_many / bootstrap_q returned).  max_records bounds every piece.  Reads every piece's
+        total (one synchronisation per sub-batch).  Returns (records, index, total)."""
+        recs, idxs, tot = [], [], 0
+        qs = [None] * self.n_sub if q is None else [x[0] if isinstance(x, tuple) else x for x in q]
+        for k, (sub, p, qk) in enumerate(zip(self.subs, self._parts(prev), qs)):
+            r, ix, n = sub.nstep_transitions(gamma, window=window, prev=p, q=qk, tail=tail, max_records=max_records)
+            n = int(n)
+            m = min(n, r.shape[0])
+            with self._on(k):
+                ix = ix[:m].clone()
+                ix[:, 1] += self.bounds[k]
+            recs.append(r[:m]); idxs.append(ix); tot += n
+        self.synchronize()
+        return torch.cat(recs), torch.cat(idxs), tot
 
     def set_exploration(self, sigma, seed=0):
         """BatchedIntersections.set_exploration for every sub-batch, each with the global index of its first environment:

@@ -40,6 +40,9 @@
 //                                     std::string &err);
 //                                                // optional, all three or none: pve_set_target_networks / pve_critic_forward /
 //                                                // pve_bootstrap_q (a NULL weight pointer of pack_target_networks = keep that image)
+//     static int   launch_nstep_scan(const pve::NstepArgs &, int block_threads, void *stream, std::string &err);
+//     static int   launch_nstep_gather(const pve::NstepArgs &, void *stream, std::string &err);
+//                                                // optional, both or none: pve_nstep_scan / pve_nstep_gather (csrc/pve_nstep.h)
 //   };
 //
 // pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
@@ -215,6 +218,19 @@ template <class B> struct backend_target_q<B, decltype((void)&B::launch_bootstra
     {
         return B::launch_bootstrap_q(ap, cp, state, obs_f32, flags, q, act7_out, n, stream, err);
     }
+};
+// The n-step pass (pve_nstep_scan / pve_nstep_gather) needs the kernels of pve_nstep.h: Backend::launch_nstep_scan /
+// launch_nstep_gather (detected by the second).  A backend without them exports the entry points all the same; they validate
+// their arguments and then refuse with PVE_ERR_INVALID.
+template <class B, class = void> struct backend_nstep {
+    static constexpr bool value = false;
+    static int scan(const NstepArgs &, int, void *, std::string &) { return -1; }
+    static int gather(const NstepArgs &, void *, std::string &) { return -1; }
+};
+template <class B> struct backend_nstep<B, decltype((void)&B::launch_nstep_gather)> {
+    static constexpr bool value = true;
+    static int scan(const NstepArgs &A, int block, void *stream, std::string &err) { return B::launch_nstep_scan(A, block, stream, err); }
+    static int gather(const NstepArgs &A, void *stream, std::string &err) { return B::launch_nstep_gather(A, stream, err); }
 };
 extern "C" {
 
@@ -507,6 +523,70 @@ int pve_bootstrap_q(pve_handle h, const void *state, const int32_t *flags, float
                                              (const unsigned char *)(h->ws + h->L.off_critic_packed), state, actor_mode(h) & 1, flags, q,
                                              act7_out, (long long)n, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_bootstrap_q: " + err);
+    return PVE_OK;
+}
+
+// pve_nstep -> NstepArgs, with every check the two entry points share
+static int nstep_args(pve_handle h, const pve_nstep *ns, bool gather, const char *who, NstepArgs &A)
+{
+    const std::string w(who);
+    if (!h || !ns) return fail(PVE_ERR_INVALID, w + ": null argument");
+    if (ns->window < 1 || ns->window > PVE_NSTEP_MAX_WINDOW) return fail(PVE_ERR_INVALID, w + ": window must be 1 .. 16");
+    if (!(ns->gamma >= 0.0 && ns->gamma <= 1.0)) return fail(PVE_ERR_INVALID, w + ": gamma must lie in [0, 1]");
+    if (ns->cur.n_ticks < 1) return fail(PVE_ERR_INVALID, w + ": cur.n_ticks must be > 0");
+    if (ns->prev.n_ticks < 0 || (ns->prev.n_ticks > 0 && ns->prev.n_ticks < ns->window))
+        return fail(PVE_ERR_INVALID, w + ": prev.n_ticks must be 0 or at least window");
+    const pve_nstep_segment *segs[2] = {&ns->cur, &ns->prev};
+    for (int k = 0; k < (ns->prev.n_ticks > 0 ? 2 : 1); k++)
+        if (!segs[k]->obs_post || !segs[k]->state_pre || !segs[k]->reward || !segs[k]->flags || !segs[k]->new_slot)
+            return fail(PVE_ERR_INVALID, w + ": a segment needs obs_post, state_pre, reward, flags and new_slot");
+    if (ns->prev.n_ticks == 0 && !ns->obs_first) return fail(PVE_ERR_INVALID, w + ": obs_first is needed when there is no prev segment");
+    if (!ns->q_boot || !ns->target || !ns->code || !ns->offsets || !ns->total)
+        return fail(PVE_ERR_INVALID, w + ": q_boot, target, code, offsets and total are needed");
+    if (gather && (ns->max_records < 0 || (ns->max_records > 0 && (!ns->records || !ns->index))))
+        return fail(PVE_ERR_INVALID, w + ": max_records must be >= 0, with records and index");
+    if (ns->block_threads < 0 || ns->block_threads > 1024 || ns->block_threads % 64)
+        return fail(PVE_ERR_INVALID, w + ": block_threads must be 0 or a multiple of 64 up to 1024");
+    const uintptr_t align = (uintptr_t)ns->cur.obs_post | (uintptr_t)ns->cur.state_pre | (uintptr_t)ns->prev.obs_post | (uintptr_t)ns->prev.state_pre |
+                            (uintptr_t)ns->obs_first | (gather ? (uintptr_t)ns->records | (uintptr_t)ns->index : 0);
+    if (align & 15) return fail(PVE_ERR_INVALID, w + ": obs_post, state_pre, obs_first, records and index must be 16-byte aligned");
+    memset(&A, 0, sizeof(A));
+    A.gamma = ns->gamma; A.window = ns->window; A.mode = ns->mode; A.n_envs = h->n_envs; A.cap = h->cap;
+    A.obs_f32 = (h->cfg.flags & PVE_CFG_OBS_F32) ? 1 : 0;
+    A.n_back = ns->prev.n_ticks < ns->window - 1 ? ns->prev.n_ticks : ns->window - 1;
+    if ((long long)(A.n_back + ns->cur.n_ticks) * h->n_envs * h->cap > 0x7fffffffLL)
+        return fail(PVE_ERR_INVALID, w + ": more than 2^31 - 1 candidate slots in one call (cut the trajectory)");
+    for (int k = 0; k < 2; k++) {
+        NstepSeg &S = k ? A.prev : A.cur;
+        S.n_ticks = segs[k]->n_ticks; S.obs_post = segs[k]->obs_post; S.state_pre = segs[k]->state_pre; S.reward = segs[k]->reward;
+        S.flags = segs[k]->flags; S.new_slot = segs[k]->new_slot;
+    }
+    A.obs_first = ns->obs_first; A.q_boot = ns->q_boot; A.target = ns->target; A.code = ns->code; A.offsets = ns->offsets;
+    A.total = (long long *)ns->total; A.max_records = ns->max_records; A.records = ns->records; A.index = ns->index;
+    if (!backend_nstep<Backend>::value) return fail(PVE_ERR_INVALID, w + ": this backend has no n-step kernels");
+    return PVE_OK;
+}
+
+int pve_nstep_scan(pve_handle h, const pve_nstep *ns)
+{
+    NstepArgs A;
+    const int rc = nstep_args(h, ns, false, "pve_nstep_scan", A);
+    if (rc != PVE_OK) return rc;
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_nstep<Backend>::scan(A, ns->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_nstep_scan: " + err);
+    return PVE_OK;
+}
+
+int pve_nstep_gather(pve_handle h, const pve_nstep *ns)
+{
+    NstepArgs A;
+    const int rc = nstep_args(h, ns, true, "pve_nstep_gather", A);
+    if (rc != PVE_OK) return rc;
+    if (A.max_records == 0) return PVE_OK;
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_nstep<Backend>::gather(A, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_nstep_gather: " + err);
     return PVE_OK;
 }
 

@@ -19,6 +19,7 @@
 #include "pve_tick_geo.h"
 #include "pve_actor.h"
 #include "pve_critic.h"
+#include "pve_nstep.h"
 
 using namespace pve;
 
@@ -1401,6 +1402,25 @@ struct Backend {
         const int grid = target_q_grid(n, 2);
         if (obs_f32) hipLaunchKernelGGL((k_target_q<float, true>), dim3(grid), dim3(256), 0, s, actor_packed, critic_packed, (const float *)state, nullptr, flags, q, act7_out, n);
         else hipLaunchKernelGGL((k_target_q<double, true>), dim3(grid), dim3(256), 0, s, actor_packed, critic_packed, (const double *)state, nullptr, flags, q, act7_out, n);
+        return check_launch(err);
+    }
+    // pve_nstep_scan: one thread per candidate start, then the offsets of the 64-slot groups in one workgroup
+    static int launch_nstep_scan(const NstepArgs &A, int block_threads, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const long long n_slots = nstep_groups(A) * NSTEP_GROUP;
+        const int block = block_threads > 0 ? block_threads : 256;
+        hipLaunchKernelGGL(k_nstep_scan, dim3((unsigned)((n_slots + block - 1) / block)), dim3(block), 0, s, A, n_slots);
+        hipLaunchKernelGGL(k_nstep_offsets, dim3(1), dim3(1024), 0, s, A.offsets, nstep_groups(A), A.total);
+        return check_launch(err);
+    }
+    static int launch_nstep_gather(const NstepArgs &A, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const long long n_slots = nstep_groups(A) * NSTEP_GROUP;
+        const dim3 grid((unsigned)((n_slots + 255) / 256));
+        if (A.obs_f32) hipLaunchKernelGGL(k_nstep_gather<float>, grid, dim3(256), 0, s, A, n_slots);
+        else hipLaunchKernelGGL(k_nstep_gather<double>, grid, dim3(256), 0, s, A, n_slots);
         return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)

@@ -9,6 +9,7 @@
 
 #include "../../include/pve_env.h"
 #include "pve_types.h"
+#include "pve_nstep.h"
 
 namespace pve {
 
