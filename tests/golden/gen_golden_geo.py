@@ -1,7 +1,7 @@
 """Golden vectors of the 4- and 8-lane geometries, made by importing the UNMODIFIED reference.
 
-Run in the build container only:   python tests/golden/gen_golden_geo.py
-Outputs (committed): tests/golden/geo_<case>.npz and tests/golden/geometry_geo.npz.
+Run in the build container only:   python tests/golden/gen_golden_geo.py [case or geometry file names: only these]
+Outputs (committed): tests/golden/geo_<case>.npz, tests/golden/geometry_geo.npz and tests/golden/geometry_geo_kw.npz.
 
 The reference ships no 4-/8-lane arrival streams (data/test holds *_12.mat only), so the streams are synthetic
 (seeded Poisson gaps clipped at 1 s, like the shipped ones) and are stored in the fixture together with the
@@ -20,14 +20,26 @@ from oracle.record import digest, get_policy, DIGEST_I_COLS, DIGEST_F_COLS  # no
 from tests.golden import ref_harness as rh  # noqa: E402
 from tests.golden.gen_golden import dense_tick_set  # noqa: E402
 
+# every constructor argument moved at once (== tests/test_ctor_kwargs.py ALL_KW, which asserts the equality)
+ALL_KW = {"dis_ctl": 120, "lane_cw": 3, "collision_thr": 3, "vM": 15, "v0": 9, "am": -2.5, "aM": 2.5, "deltaT": 0.2, "vm": 6}
 CASES = [
-    # name, lane_num, policy, ticks, mean gap [s], seed
-    ("g4_zero", 4, "zero", 1000, 2.0, 41),
-    ("g4_sin2", 4, "sin2", 1200, 1.5, 42),
-    ("g4_sin3", 4, "sin3", 800, 1.2, 43),
-    ("g8_zero", 8, "zero", 1000, 2.0, 81),
-    ("g8_sin2", 8, "sin2", 1200, 1.5, 82),
-    ("g8_sin3", 8, "sin3", 800, 1.2, 83),
+    # name, lane_num, policy, ticks, mean gap [s], seed, constructor arguments
+    ("g4_zero", 4, "zero", 1000, 2.0, 41, {}),
+    ("g4_sin2", 4, "sin2", 1200, 1.5, 42, {}),
+    ("g4_sin3", 4, "sin3", 800, 1.2, 43, {}),
+    ("g8_zero", 8, "zero", 1000, 2.0, 81, {}),
+    ("g8_sin2", 8, "sin2", 1200, 1.5, 82, {}),
+    ("g8_sin3", 8, "sin3", 800, 1.2, 83, {}),
+    # non-default constructor arguments under the pseudo-random +-3 tape (collisions and dead-locks); vm = 6 is what the
+    # shipped checkpoint was trained with (model_data/baseline/args.txt: lane_num 4; main.py:230)
+    ("g4_rand_kw", 4, "rand3", 300, 1.2, 904, ALL_KW),
+    ("g8_rand_kw", 8, "rand3", 300, 1.2, 908, ALL_KW),
+    ("g4_rand_vm6", 4, "rand3", 400, 1.2, 904, {"vm": 6}),
+]
+# known answers of the geometry tables: file -> constructor arguments
+GEOMETRY = [
+    ("geometry_geo", {}),
+    ("geometry_geo_kw", {"lane_cw": 3, "dis_ctl": 120}),
 ]
 DENSE_FIELDS = ("ids", "nbr", "reward", "obs0", "coll_pv", "deleted", "jerks", "veh_i", "veh_f",
                 "heads", "veh_num", "veh_rec", "intent")
@@ -39,9 +51,9 @@ def make_stream(lane_num, rows, mean, seed):
     return np.cumsum(gaps, axis=0), rng.integers(0, 2, size=(rows, lane_num)).astype(np.int32)
 
 
-def gen_case(name, lane_num, pol, ticks, mean, seed):
+def gen_case(name, lane_num, pol, ticks, mean, seed, ctor):
     arr, choice = make_stream(lane_num, 400, mean, seed)
-    ref = rh.GeoRefRunner(arr, lane_num, get_policy(pol), choice=choice, want_state=True)
+    ref = rh.GeoRefRunner(arr, lane_num, get_policy(pol), choice=choice, want_state=True, **ctor)
     dense = dense_tick_set(ticks)
     state_ticks = [3, ticks // 2, ticks - 1]
     out = {}
@@ -72,7 +84,7 @@ def gen_case(name, lane_num, pol, ticks, mean, seed):
     out["state_ticks"] = np.array(state_ticks, np.int32)
     out["guard_hits"] = np.array(ref.guard_hits, np.int32)
     out["meta"] = np.array(json.dumps(dict(name=name, lane_num=lane_num, stream="synthetic mean %.1f s seed %d" % (mean, seed),
-                                           policy=pol, ticks=ticks, ctor={}, numpy=np.__version__)))
+                                           policy=pol, ticks=ticks, ctor=dict(ctor), numpy=np.__version__)))
     path = os.path.join(HERE, "geo_" + name + ".npz")
     np.savez_compressed(path, **out)
     print("%-10s lanes %2d ticks %4d alive-steps %6d ctl-steps %6d id_seq %3d passed %3d collided %3d locks %4d "
@@ -80,13 +92,20 @@ def gen_case(name, lane_num, pol, ticks, mean, seed):
                                  dig_i[-1, 3], n_coll, n_lock, ref.guard_hits, os.path.getsize(path) // 1024))
 
 
-def gen_geometry():
-    """Known answers of get_p / get_virtual_distance for lane_num 4 and 8, sampled through the reference."""
+def gen_geometry(only=()):
+    """Known answers of get_p / get_virtual_distance (and lane_info) for lane_num 4 and 8, sampled through the reference:
+    one file per entry of GEOMETRY (default arguments; lane_cw = 3 with dis_ctl = 120)."""
+    for fname, ctor in GEOMETRY:
+        if not only or fname in only:
+            gen_geometry_file(fname, **ctor)
+
+
+def gen_geometry_file(fname, dis_ctl=150, **ctor):
     tis = rh.import_reference()
     out = {}
     for ln in (4, 8):
         arr, _ = make_stream(ln, 50, 3.0, 7)
-        env = tis.TrafficInteraction(arr, 150, rh.default_args(), show_col=False, virtual_l=True, lane_num=ln)
+        env = tis.TrafficInteraction(arr, dis_ctl, rh.default_args(), show_col=False, virtual_l=True, lane_num=ln, **ctor)
         li = np.array(env.lane_info, np.float64)
         ps = np.concatenate([np.linspace(-140, 170, 125), np.linspace(0, 21, 85),
                              np.array([0.0, 1e-9, li[0][1], li[1][1], li[2][1], li[0][1] + 1e-9, li[2][1] - 1e-9])])
@@ -108,13 +127,13 @@ def gen_geometry():
                     if ch:
                         vd[ego, other, k] = d[0]
         out["ps%d" % ln], out["get_p%d" % ln], out["vd%d" % ln], out["lane_info%d" % ln] = ps, gp, vd, li
-    np.savez_compressed(os.path.join(HERE, "geometry_geo.npz"), **out)
-    print("geometry_geo.npz written")
+    np.savez_compressed(os.path.join(HERE, fname + ".npz"), **out)
+    print(fname + ".npz written")
 
 
 if __name__ == "__main__":
-    only = sys.argv[1:]
-    gen_geometry()
+    only = sys.argv[1:]           # case names (g4_zero, ...) and / or geometry files (geometry_geo_kw); none: everything
+    gen_geometry(only)
     for c in CASES:
         if not only or c[0] in only:
             gen_case(*c)

@@ -227,7 +227,12 @@ class GeoRefRunner(ObjRunner):
         self._tis = tis
         self._saved_random = tis.random
         tis.random = shim
-        env = _Spy(arrive_time, 150, default_args(), show_col=False, virtual_l=True, lane_num=lane_num, **ctor_kw)
+        # the constructor's positional dis_ctl and args.collision_thr, as in RefRunner
+        ctor_kw = dict(ctor_kw)
+        dis_ctl = ctor_kw.pop("dis_ctl", 150)
+        args = default_args()
+        args.collision_thr = ctor_kw.pop("collision_thr", args.collision_thr)
+        env = _Spy(arrive_time, dis_ctl, args, show_col=False, virtual_l=True, lane_num=lane_num, **ctor_kw)
         ObjRunner.__init__(self, env, policy, want_state, guard=True)
         orig = env.virtual_lane_search_closer
 

@@ -10,7 +10,9 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASE_NAMES = ["s1000_zero", "s1000_sin1", "s200_sin1", "s1200_sin1", "s1200_zero", "s400_sin2",
               "s1000_sin3", "s1000_sin1_vm6", "s1000_rand_kw", "s1000_actor"]
 # 4- / 8-lane geometries: synthetic streams + intention draws stored in the fixture
-GEO_CASE_NAMES = ["geo_g4_zero", "geo_g4_sin2", "geo_g4_sin3", "geo_g8_zero", "geo_g8_sin2", "geo_g8_sin3"]
+GEO_CASE_NAMES = ["geo_g4_zero", "geo_g4_sin2", "geo_g4_sin3", "geo_g8_zero", "geo_g8_sin2", "geo_g8_sin3",
+                  # non-default constructor arguments (meta["ctor"]): all of them together; vm = 6, the trained configuration
+                  "geo_g4_rand_kw", "geo_g8_rand_kw", "geo_g4_rand_vm6"]
 DENSE_FIELDS = ("ids", "nbr", "reward", "obs0", "coll_pv", "deleted", "jerks", "veh_i", "veh_f",
                 "heads", "veh_num", "veh_rec")
 

@@ -314,10 +314,12 @@ def check_general_path_equals_fast_path(backend, n_envs=6, capacity=128, ticks=3
 
 
 def check_geo_fuzz_vs_oracle(backend, lane_num, n_envs, capacity, ticks, rate, seed, action_scale=3.0, quantize=None,
-                             arrivals=None):
+                             arrivals=None, cfg=None):
     """Random action tapes on a batch of 4- or 8-lane envs (own arrival + intention streams), fused ticks, every env
     against its own sequential oracle every tick: processing order, controlled set, neighbours, rewards,
-    observations, collision counters, lock counts; full persistent state at the end."""
+    observations, collision counters, lock counts; full persistent state at the end.
+    cfg: constructor arguments (vm, dis_ctl, lane_cw, ...: ref :21-23) for every batch and every oracle."""
+    cfg = cfg or {}
     from oracle.oracle_geo import OracleGeoEnv
     from pve_mcc_amd.arrivals import synthetic_intentions
     rng = np.random.default_rng(seed)
@@ -325,9 +327,9 @@ def check_geo_fuzz_vs_oracle(backend, lane_num, n_envs, capacity, ticks, rate, s
                                                                    lane_num=lane_num)
     ch = synthetic_intentions(n_envs, arr.shape[1], seed=seed, lane_num=lane_num) if lane_num == 8 else None
     b = make_batch(arr, n_envs, capacity, backend, lane_num=lane_num, intentions=ch,
-                   outputs=("obs_post", "obs_pre", "reward", "flags", "nbr", "env_out", "new_slot", "lanej"))
+                   outputs=("obs_post", "obs_pre", "reward", "flags", "nbr", "env_out", "new_slot", "lanej"), **cfg)
     b.reset()
-    oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e]) for e in range(n_envs)]
+    oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e], **cfg) for e in range(n_envs)]
     tot_coll = tot_lock = 0
     def run_ticks():
         nonlocal tot_coll, tot_lock
@@ -577,10 +579,11 @@ def check_step_many(backend, source, n_envs=5, capacity=128, seed=71, chunks=(1,
 
 
 def check_step_many_geo(backend, lane_num, n_envs=5, capacity=128, seed=75, chunks=(1, 7, 40, 3, 60), rate=None,
-                        trajectory_chunk=12, quantize=None, source="pool", persistent=False):
+                        trajectory_chunk=12, quantize=None, source="pool", persistent=False, cfg=None):
     """pve_step_many for the 4- / 8-lane layouts (k_rollout_geo: the general-geometry tick resident on the chip) == single
     pve_step_all ticks of k_tick_geo, bit for bit: persistent state, headers (incl. the spawn counter intention_re and
-    the stale list heads), observation rows, last-tick outputs and, in trajectory mode, every tick's outputs."""
+    the stale list heads), observation rows, last-tick outputs and, in trajectory mode, every tick's outputs.
+    cfg: constructor arguments (vm, dis_ctl, lane_cw, ...) for both batches."""
     from pve_mcc_amd.arrivals import synthetic_intentions
     n_pool = 5
     rng = np.random.default_rng(seed)
@@ -589,7 +592,7 @@ def check_step_many_geo(backend, lane_num, n_envs=5, capacity=128, seed=75, chun
     arr = synthetic_arrivals(n_envs, rate=rate, horizon_s=total * 0.1 + 30, seed=seed, lane_num=lane_num)
     ch = synthetic_intentions(n_envs, arr.shape[1], seed=seed, lane_num=lane_num) if lane_num == 8 else None
     outs = ("obs_post", "reward", "flags", "nbr", "new_slot", "env_out", "lanej")
-    kw = dict(lane_num=lane_num, intentions=ch, outputs=outs)
+    kw = dict(lane_num=lane_num, intentions=ch, outputs=outs, **(cfg or {}))
     if lane_num == 12:
         kw["general_path"] = True
     one = make_batch(arr, n_envs, capacity, backend, **kw)
@@ -656,12 +659,14 @@ def check_step_many_geo(backend, lane_num, n_envs=5, capacity=128, seed=75, chun
 
 
 def check_step_many_geo_actor(backend, lane_num, n_envs=6, capacity=128, seed=77, chunks=(1, 9, 30, 4, 45), rate=None,
-                              trajectory_chunk=11, obs_dtype=torch.float64, persistent=False, oracle_ticks=0, strict=True):
+                              trajectory_chunk=11, obs_dtype=torch.float64, persistent=False, oracle_ticks=0, strict=True, cfg=None):
     """The closed loop for the 4- / 8-lane layouts (main.py:398-441 drives every lane_num; the shipped checkpoint's args.txt
     records lane_num = 4): pve_step_many(PVE_SRC_ACTOR) -- the actor inside k_rollout_geo<.., ACT[, PERS]> -- == step_with_actor
     ticks (actor launch + k_tick_geo), bit for bit: persistent state, headers, observation rows, last-tick outputs and, in
     trajectory mode, every tick's outputs.  oracle_ticks > 0: first, for that many ticks, the two-launch form itself against
-    the sequential general-geometry oracle, which is handed the actions the device actor produced (rewards + state)."""
+    the sequential general-geometry oracle, which is handed the actions the device actor produced (rewards + state).
+    cfg: constructor arguments (vm, dis_ctl, lane_cw, ...) for both batches and every oracle."""
+    cfg = cfg or {}
     from oracle.actor_np import flat_weights, load_weights
     from pve_mcc_amd.arrivals import synthetic_intentions
     rate = rate or {8: 1300.0, 4: (1500.0 if capacity == 128 else 1000.0)}[lane_num]
@@ -669,7 +674,7 @@ def check_step_many_geo_actor(backend, lane_num, n_envs=6, capacity=128, seed=77
     arr = synthetic_arrivals(n_envs, rate=rate, horizon_s=total * 0.1 + 30, seed=seed, lane_num=lane_num)
     ch = synthetic_intentions(n_envs, arr.shape[1], seed=seed, lane_num=lane_num) if lane_num == 8 else None
     outs = ("obs_post", "reward", "flags", "nbr", "new_slot", "env_out", "lanej")
-    kw = dict(lane_num=lane_num, intentions=ch, outputs=outs, obs_dtype=obs_dtype)
+    kw = dict(lane_num=lane_num, intentions=ch, outputs=outs, obs_dtype=obs_dtype, **cfg)
     one = make_batch(arr, n_envs, capacity, backend, **kw)
     many = make_batch(arr, n_envs, capacity, backend, **kw)
     w = flat_weights(load_weights())
@@ -678,7 +683,7 @@ def check_step_many_geo_actor(backend, lane_num, n_envs=6, capacity=128, seed=77
         b.set_actor(w)
     if oracle_ticks:
         from oracle.oracle_geo import OracleGeoEnv
-        oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e]) for e in range(n_envs)]
+        oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e], **cfg) for e in range(n_envs)]
         for t in range(oracle_ticks):
             acts = _np(one.act()).copy()
             out = one.step_with_actor()
@@ -743,7 +748,8 @@ def check_step_many_geo_actor(backend, lane_num, n_envs=6, capacity=128, seed=77
 
 
 def check_step_many_state_rows(backend, n_envs=3, capacity=128, rate=None, calls=(40, 25, 60, 35), seed=81, n_pool=7,
-                               obs_dtype=torch.float64, chunk=0, source="pool", min_ctl_per_tick=5, lane_num=12, persistent=False):
+                               obs_dtype=torch.float64, chunk=0, source="pool", min_ctl_per_tick=5, lane_num=12, persistent=False,
+                               cfg=None):
     """Training outputs on the fast path (lane_num 4 / 8: f3 x f4):
     pve_step_many trajectory roll-outs with state_pre -- the 7 x 28 states with fresh / stale neighbour rows (ref
     :1325-1337) and the 7-action vectors (column 2, ref :290) -- compared with the oracle at EVERY tick of every env (ids,
@@ -752,7 +758,9 @@ def check_step_many_state_rows(backend, n_envs=3, capacity=128, rate=None, calls
     layouts process (and list) the vehicles in (lane, intention, j) order (ref :233-275).
     persistent=True (round 5; lane_num 12): the trainer's roll-out through the work queue -- k_rollout<.., TRAIN, PERS>: the stale
     rows of an item's first tick are what the previous item of the intersection (another workgroup) stored.
-    source="table": actions by (tick, vehicle id) (k_rollout<.., TRAIN, IDT>)."""
+    source="table": actions by (tick, vehicle id) (k_rollout<.., TRAIN, IDT>).
+    cfg: constructor arguments (vm, dis_ctl, lane_cw, ...) for the batch and every oracle."""
+    cfg = cfg or {}
     from pve_mcc_amd import _capi
     from pve_mcc_amd.arrivals import synthetic_intentions
     rng = np.random.default_rng(seed)
@@ -762,7 +770,7 @@ def check_step_many_state_rows(backend, n_envs=3, capacity=128, rate=None, calls
     ch = synthetic_intentions(n_envs, arr.shape[1], seed=seed, lane_num=lane_num) if lane_num == 8 else None
     outs = ("obs_post", "obs_pre", "state_pre", "reward", "flags", "nbr", "lanej", "env_out", "new_slot")
     kw = dict(lane_num=lane_num, intentions=ch) if lane_num != 12 else {}
-    b = make_batch(arr, n_envs, capacity, backend, outputs=outs, obs_dtype=obs_dtype, **kw)
+    b = make_batch(arr, n_envs, capacity, backend, outputs=outs, obs_dtype=obs_dtype, **kw, **cfg)
     b.reset()
     pool_np = rng.uniform(-3, 3, size=(n_pool, n_envs, capacity)).astype(np.float32).astype(np.float64)
     if source == "pool":
@@ -771,10 +779,10 @@ def check_step_many_state_rows(backend, n_envs=3, capacity=128, rate=None, calls
     if source == "table":
         b.set_action_table(torch.as_tensor(table_np))
     if lane_num == 12:
-        oracles = [OracleEnv(arr[e]) for e in range(n_envs)]
+        oracles = [OracleEnv(arr[e], **cfg) for e in range(n_envs)]
     else:
         from oracle.oracle_geo import OracleGeoEnv
-        oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e]) for e in range(n_envs)]
+        oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e], **cfg) for e in range(n_envs)]
     tol = 1e-9 if obs_dtype == torch.float64 else 2e-6          # float32 rows: relative round-off of the stored values
     t, n_ctl_total = 0, 0
     ring = [b.alloc_trajectory(max(calls)) for _ in range(2)]
@@ -819,18 +827,20 @@ def check_step_many_state_rows(backend, n_envs=3, capacity=128, rate=None, calls
 
 
 def check_closed_loop_state_rows(backend, n_envs=6, capacity=128, rate=1000.0, calls=(30, 17, 40), chunk=7, seed=87,
-                                 obs_dtype=torch.float32, persistent=False, lane_num=12, want_launch=None):
+                                 obs_dtype=torch.float32, persistent=False, lane_num=12, want_launch=None, cfg=None):
     """The trainer's closed-loop roll-out: pve_step_many(PVE_SRC_ACTOR, trajectory = 1) with the training outputs (obs_pre,
     state_pre: k_rollout<.., ACT, TRAIN[, PERS]>) == step_with_actor ticks (actor launch + k_tick with its own STATE phase), bit
-    for bit: rows, 7 x 28 states, rewards, flags of every tick, and the persistent state after every call."""
+    for bit: rows, 7 x 28 states, rewards, flags of every tick, and the persistent state after every call.
+    cfg: constructor arguments (vm, dis_ctl, lane_cw, ...) for both batches."""
+    cfg = cfg or {}
     from oracle.actor_np import flat_weights, load_weights
     from pve_mcc_amd.arrivals import synthetic_intentions
     arr = synthetic_arrivals(n_envs, rate=rate, horizon_s=sum(calls) * 0.1 + 30, seed=seed, lane_num=lane_num)
     geo = dict(lane_num=lane_num, intentions=synthetic_intentions(n_envs, arr.shape[1], seed=seed, lane_num=lane_num) if lane_num == 8 else None) \
         if lane_num != 12 else {}
     outs = ("obs_post", "obs_pre", "state_pre", "reward", "flags", "nbr", "new_slot", "env_out")
-    one = make_batch(arr, n_envs, capacity, backend, outputs=outs, obs_dtype=obs_dtype, **geo)
-    many = make_batch(arr, n_envs, capacity, backend, outputs=outs, obs_dtype=obs_dtype, **geo)
+    one = make_batch(arr, n_envs, capacity, backend, outputs=outs, obs_dtype=obs_dtype, **geo, **cfg)
+    many = make_batch(arr, n_envs, capacity, backend, outputs=outs, obs_dtype=obs_dtype, **geo, **cfg)
     w = flat_weights(load_weights())
     n_ctl = 0
     for b in (one, many):

@@ -14,13 +14,14 @@ from tests.parity_util import GoldenCase, check_against_golden
 
 def make_env(case, backend):
     from pve_mcc_amd.traffic_interaction_scene import TrafficInteraction
-    args = types.SimpleNamespace(collision_thr=2, o_agent_num=6, c_mode="closer")
-    kw = dict(case.ctor)
+    kw = dict(case.ctor)               # the positional dis_ctl and args.collision_thr are constructor arguments of a fixture too
+    args = types.SimpleNamespace(collision_thr=kw.pop("collision_thr", 2), o_agent_num=6, c_mode="closer")
+    dis_ctl = kw.pop("dis_ctl", 150)
     if backend == "emu":
         kw.update(device="cpu", _lib=emulator_lib())
     if case.lane_num == 8:
         kw["intentions"] = case.choice
-    return TrafficInteraction(case.arrive, 150, args, show_col=False, virtual_l=True, lane_num=case.lane_num, **kw)
+    return TrafficInteraction(case.arrive, dis_ctl, args, show_col=False, virtual_l=True, lane_num=case.lane_num, **kw)
 
 
 def run_compat(name, ticks, backend):
@@ -42,7 +43,7 @@ def test_compat_class_reproduces_golden(name, ticks):
     assert env.id_seq > 0 and env.deltaT == 0.1 and env.lane_num == 12
 
 
-@pytest.mark.parametrize("name,ticks,lanes", [("geo_g4_sin2", 500, 4), ("geo_g8_sin3", 500, 8)])
+@pytest.mark.parametrize("name,ticks,lanes", [("geo_g4_sin2", 500, 4), ("geo_g8_sin3", 500, 8), ("geo_g4_rand_vm6", 400, 4)])
 def test_compat_class_4_and_8_lanes_reproduce_golden(name, ticks, lanes):
     """SURVEY §8 f4 through the drop-in class: `ids` / rewards / states come out in (lane, intention, j) order."""
     env = run_compat(name, ticks, "emu")

@@ -212,7 +212,8 @@ def test_gpu_side_stream_and_two_handles():
 
 
 # ---------------------------------------------------------------- 4- / 8-lane layouts (k_tick_geo)
-@pytest.mark.parametrize("name", ["geo_g4_zero", "geo_g4_sin2", "geo_g4_sin3", "geo_g8_zero", "geo_g8_sin2", "geo_g8_sin3"])
+@pytest.mark.parametrize("name", ["geo_g4_zero", "geo_g4_sin2", "geo_g4_sin3", "geo_g8_zero", "geo_g8_sin2", "geo_g8_sin3",
+                                  "geo_g4_rand_kw", "geo_g8_rand_kw", "geo_g4_rand_vm6"])
 def test_gpu_geo_split_protocol_matches_golden(name):
     case = GoldenCase(name)
     assert scenarios.check_geo_golden(case, BACKEND) == case.ticks
@@ -267,7 +268,7 @@ def test_gpu_left_neighbours_one_ulp_apart_share_a_distance():
     scenarios.check_geo_fuzz_vs_oracle(BACKEND, 8, n_envs=24, capacity=128, ticks=160, rate=1600.0, seed=3110, quantize=1.0)
 
 
-@pytest.mark.parametrize("name,ticks", [("geo_g4_sin2", 400), ("geo_g8_sin3", 400)])
+@pytest.mark.parametrize("name,ticks", [("geo_g4_sin2", 400), ("geo_g8_sin3", 400), ("geo_g4_rand_vm6", 400)])
 def test_gpu_compat_class_4_and_8_lanes(name, ticks):
     from tests.test_compat_class import run_compat
     env = run_compat(name, ticks, "hip")

@@ -29,10 +29,28 @@ def test_geo_oracle_12_lanes_equals_the_pinned_12_lane_vectors(name):
 
 @pytest.mark.parametrize("lane_num", [4, 8])
 def test_geo_oracle_geometry_known_answers(lane_num):
-    g = np.load(os.path.join(GOLDEN_DIR, "geometry_geo.npz"))
+    check_geometry_known_answers("geometry_geo.npz", lane_num)
+
+
+@pytest.mark.parametrize("lane_num", [4, 8])
+def test_geo_oracle_geometry_known_answers_lane_cw_3_dis_ctl_120(lane_num):
+    """The same tables with lane_cw = 3 and dis_ctl = 120 (sampled through the reference into geometry_geo_kw.npz): pins the
+    oracle's derived geometry where the reference is not at hand, so that the device tests under non-default constructor
+    arguments (test_ctor_kwargs.py) compare with a pinned oracle."""
+    g = np.load(os.path.join(GOLDEN_DIR, "geometry_geo_kw.npz"))
+    d = np.load(os.path.join(GOLDEN_DIR, "geometry_geo.npz"))
+    li = g["lane_info%d" % lane_num]
+    assert li.shape == (3, 3) and not np.allclose(li, d["lane_info%d" % lane_num])      # (the arguments did move the geometry,
+    assert np.all(li[:, 0] < 120) and np.all(li[:, 0] == -li[:, 2])                     #  and the sample points its breakpoints)
+    assert not np.array_equal(g["ps%d" % lane_num], d["ps%d" % lane_num])
+    check_geometry_known_answers("geometry_geo_kw.npz", lane_num, lane_cw=3, dis_ctl=120)
+
+
+def check_geometry_known_answers(fname, lane_num, **ctor):
+    g = np.load(os.path.join(GOLDEN_DIR, fname))
     ps, gp, vd = g["ps%d" % lane_num], g["get_p%d" % lane_num], g["vd%d" % lane_num]
     arr = np.cumsum(np.full((4, lane_num), 50.0), axis=0)
-    env = OracleGeoEnv(arr, lane_num)
+    env = OracleGeoEnv(arr, lane_num, **ctor)
     n_xy = 0
     for lane in range(lane_num):
         for m in range(3):
