@@ -1330,7 +1330,7 @@ struct Backend {
                                int n_envs, int cap, bool exact_f32, const int32_t *ids, const ActionNoise &nz, hipStream_t s)
     {
         // persistent workgroups of 4 waves (the parameters are staged in LDS once per workgroup): 4 per CU, one wave
-        // per intersection at a time
+        // per intersection at a time (a wave's second intersection, n_envs > 4096: tests/test_gpu_actor_streaming.py)
         static const int wgs = [] { const char *g = PVE_KNOB("PVE_ACTOR_GRID"); const int v = g ? atoi(g) : 0; return v > 0 ? v : 1024; }();
         const int grid = (n_envs + 3) / 4 < wgs ? (n_envs + 3) / 4 : wgs;
         if (exact_f32) {
@@ -1382,7 +1382,7 @@ struct Backend {
     // persistent workgroups of 4 waves, every wave walks chunks of 64 rows: as many workgroups as stay resident (LDS: the
     // bootstrap kernel holds both packed networks, 2 per CU; the critic alone 4 per CU), never more than there are chunks
     static int target_q_grid(long long n, int per_cu)
-    {
+    {   // (mirrored by tests/target_q_walk.py, the host model of the walk behind the tests with several chunks per wave)
         const long long want = (n + 255) / 256, cap = 256LL * per_cu;
         return (int)(want < cap ? want : cap);
     }

@@ -7,7 +7,10 @@ Bars (none of them taken from what the kernels return):
               split-half operands.
   bootstrap:  3 x spread_critic + sens x ACTION_TOL.  ACTION_TOL (5e-4) is the action error the project already accepts for the
               device actor; sens = max sum_k |dQ/da_k| of the reference's target critic (15.6) pushes it through to Q.
-Every test prints the maximum it measured before it asserts."""
+Every test prints the maximum it measured before it asserts.
+
+Section 6 runs k_target_q beyond one 64-row chunk per wave (the pending ring across chunks; tests/target_q_walk.py is the host
+model of that walk and builds the inputs, tests/test_target_q_walk.py shows on the CPU that they reach the ring's paths)."""
 import numpy as np
 import pytest
 import torch
@@ -16,6 +19,7 @@ from oracle.actor_np import flat_weights
 from pve_mcc_amd import _capi, critic
 from pve_mcc_amd.arrivals import synthetic_arrivals
 from tests import actor_scenarios as A
+from tests import target_q_walk as TQ
 from tests.critic_scenarios import load_critic_golden
 from tests.hip_adapter import _np, make_batch
 
@@ -221,3 +225,92 @@ def test_gpu_bootstrap_over_a_trajectory():
         assert torch.equal(traj[k], traj0[k]), k
     for f in ("p", "v", "a", "id", "meta", "step"):
         assert torch.equal(b.state_field(f), b0.state_field(f)), f
+
+
+# ------------------------------------------------------------------ 6. more than one chunk per wave: the pending ring across chunks
+SENT_Q, SENT_A = np.float32(-12345.5), np.float32(777.25)
+
+
+def big_bootstrap_inputs(b, g, n):
+    """(state [n, 7, 28] built ON the device from the uploaded fixture, flags, row map, evaluated mask) of the big call"""
+    idx, flags = TQ.row_map(n, g.n), TQ.bootstrap_flags(n)
+    fixture = torch.as_tensor(g.states).to(b.device, b.obs_dtype)
+    big = fixture.index_select(0, torch.as_tensor(idx).to(b.device))
+    return big, torch.as_tensor(flags).to(b.device), idx, TQ.evaluated(flags)
+
+
+def sentinel_buffers(b, n):
+    return (torch.full((n + 64,), float(SENT_Q), dtype=torch.float32, device=b.device),
+            torch.full(((n + 64) * 7,), float(SENT_A), dtype=torch.float32, device=b.device))
+
+
+@pytest.mark.parametrize("obs_dtype,n", [(torch.float32, TQ.N_BOOT_F32), (torch.float64, TQ.N_BOOT_F64)])
+def test_gpu_bootstrap_many_chunks_per_wave(obs_dtype, n):
+    """Three chunks per wave at 512 workgroups, chunk densities 0.25 .. 1: rows carried into the next chunk, ring writes across
+    index 127 -> 0, a 95-entry backlog, tiles mixing rows of two chunks, left-overs flushed behind a chunk that accepted nothing.
+    Expected: the kernel's own one-chunk-per-wave results on the fixture's rows (the path pinned to the graph above), bit for
+    bit -- each vehicle is its own column of the matrix products, so its tile company does not matter (section 4 asserts the
+    same between masked and unmasked runs) -- and, independently of the kernel, the graph in float64 within the bars above."""
+    g = load_critic_golden()
+    b = batch(obs_dtype)
+    assert TQ.target_q_grid(g.n, TQ.BOOT_PER_CU) * 4 * 64 >= g.n and TQ.target_q_grid(n, TQ.BOOT_PER_CU) * 4 * 64 * 2 < n
+    q_small, a_small = b.bootstrap_q(torch.as_tensor(g.states))           # flags = None, one chunk per wave
+    q_small, a_small = _np(q_small), _np(a_small)
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    big, flags, idx, ev = big_bootstrap_inputs(b, g, n)
+    qbuf, abuf = sentinel_buffers(b, n)
+    b.bootstrap_q(big, flags, out=qbuf[:n], actions_out=abuf[:n * 7].view(n, 7))
+    # the same call without an output buffer for the actions (the raw entry point, as in section 4)
+    qbuf2 = torch.full((n + 64,), float(SENT_Q), dtype=torch.float32, device=b.device)
+    rc = b.lib.pve_bootstrap_q(b._h, big.data_ptr(), flags.data_ptr(), qbuf2.data_ptr(), None, n)
+    b.synchronize()
+    held = (torch.cuda.max_memory_allocated() - base) / 1e6
+    q, a7, q2 = _np(qbuf), _np(abuf), _np(qbuf2)
+    del big, qbuf, abuf, qbuf2
+    print("bootstrap_q, %d rows, %s, grid %d: %.0f MB on the device, %d evaluated rows (%.3f); walk %s"
+          % (n, obs_dtype, TQ.target_q_grid(n, TQ.BOOT_PER_CU), held, ev.sum(), ev.mean(), TQ.counters(TQ.bootstrap_walk(n))))
+    assert np.all(q[n:] == SENT_Q) and np.all(a7[n * 7:] == SENT_A), "wrote behind q[n] / act7_out[n]"
+    q, a7 = q[:n], a7[:n * 7].reshape(n, 7)
+    assert np.all(bits32(q[~ev]) == 0) and np.all(bits32(a7[~ev]) == 0), "masked rows must be exactly 0"
+    wrong_q = np.flatnonzero(ev & (bits32(q) != bits32(q_small[idx])))
+    wrong_a = np.flatnonzero(ev & (bits32(a7) != bits32(a_small[idx])).any(axis=1))
+    assert len(wrong_q) == 0 and len(wrong_a) == 0, "rows %s / %s (chunks %s) differ from the one-chunk call" % (
+        wrong_q[:8], wrong_a[:8], np.unique(np.concatenate([wrong_q, wrong_a]) // 64)[:8])
+    worst_a = float(np.abs(a7.astype(np.float64) - g.boot_act7_f64[idx])[ev].max())
+    worst_q = float(np.abs(q.astype(np.float64) - g.boot_q_f64[idx])[ev].max())
+    print("bootstrap_q, %d rows, %s: max |a - graph| = %.3e (bar %.1e), max |q - graph f64| = %.3e (bar %.3e)"
+          % (n, obs_dtype, worst_a, ACTION_TOL, worst_q, boot_bar(g)))
+    assert worst_a <= ACTION_TOL and worst_q <= boot_bar(g)
+    assert rc == 0 and np.array_equal(bits32(q2[:n]), bits32(q)) and np.all(q2[n:] == SENT_Q), "actions_out = NULL changes q"
+
+
+@pytest.mark.parametrize("obs_dtype", DTYPES)
+def test_gpu_critic_q_many_chunks_per_wave(obs_dtype):
+    """The critic alone (flags = NULL: whole chunks only) at 2 x 262 144 + 3 x 64 + 17 rows: 4 waves of the 1024 workgroups take
+    a third chunk (their ring wraps with it), the last chunk is partial."""
+    g = load_critic_golden()
+    b = batch(obs_dtype, "critic")
+    n = TQ.N_CRITIC
+    idx = TQ.row_map(n, len(g.given_rows), seed=12)
+    q_small = _np(b.critic_q(torch.as_tensor(g.given_rows), torch.as_tensor(g.given_act7)))
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    idx_dev = torch.as_tensor(idx).to(b.device)
+    rows = torch.as_tensor(g.given_rows).to(b.device, b.obs_dtype).index_select(0, idx_dev)
+    acts = torch.as_tensor(g.given_act7).to(b.device).index_select(0, idx_dev)
+    qbuf, _ = sentinel_buffers(b, n)
+    b.critic_q(rows, acts, out=qbuf[:n])
+    b.synchronize()
+    held = (torch.cuda.max_memory_allocated() - base) / 1e6
+    q = _np(qbuf)
+    del rows, acts, qbuf
+    print("critic_q, %d rows, %s, grid %d: %.0f MB on the device; walk %s"
+          % (n, obs_dtype, TQ.target_q_grid(n, TQ.CRITIC_PER_CU), held, TQ.counters(TQ.critic_walk(n))))
+    assert np.all(q[n:n + 64] == SENT_Q), "wrote behind q[n]"
+    q = q[:n]
+    wrong = np.flatnonzero(bits32(q) != bits32(q_small[idx]))
+    assert len(wrong) == 0, "rows %s (chunks %s) differ from the one-chunk call" % (wrong[:8], np.unique(wrong // 64)[:8])
+    worst = float(np.abs(q.astype(np.float64) - g.critic_q_f64[idx]).max())
+    print("critic_q, %d rows, %s: max |q - graph f64| = %.3e (bar %.3e)" % (n, obs_dtype, worst, q_bar(g)))
+    assert worst <= q_bar(g)

@@ -29,12 +29,13 @@ def bits32(x):
     return np.ascontiguousarray(np.asarray(x, np.float32)).view(np.uint32)
 
 
-def batch(cap, f32):
+def batch(cap, f32, n_envs=E):
     """One small handle per (capacity, row type): the pass only takes n_envs, capacity, the row type and the stream from it"""
-    if (cap, f32) not in _batches:
-        arr = synthetic_arrivals(E, rate=500.0, horizon_s=20.0, seed=3)
-        _batches[cap, f32] = make_batch(arr, E, cap, "hip", outputs=("obs_post", "flags"), obs_dtype=torch.float32 if f32 else torch.float64)
-    return _batches[cap, f32]
+    if (cap, f32, n_envs) not in _batches:
+        arr = synthetic_arrivals(n_envs, rate=500.0, horizon_s=20.0, seed=3)
+        _batches[cap, f32, n_envs] = make_batch(arr, n_envs, cap, "hip", outputs=("obs_post", "flags"),
+                                                obs_dtype=torch.float32 if f32 else torch.float64)
+    return _batches[cap, f32, n_envs]
 
 
 def dev(seg, b):
@@ -88,6 +89,31 @@ def test_gpu_windows(window):
     for tail in (False, True):
         assert check(*run_both(b, tr, 17, 23, 0, window=window, tail=tail, gamma=0.8)) > 0
         assert check(*run_both(b, tr, 0, 23, None, window=window, tail=tail, gamma=1.0)) > 0
+
+
+# ------------------------------------------------------------------ 1b. k_nstep_offsets with runs of more than one group
+@pytest.mark.parametrize("n,ragged", [(40, False), (5, True)])
+def test_gpu_offsets_with_runs_of_several_groups(n, ragged):
+    """k_nstep_offsets is ONE workgroup of 1024 threads, each owning per = ceil(n_groups / 1024) consecutive group counts; up
+    to 1024 groups (every case above) per == 1.  67 intersections x 64 slots, ticks 20 .. 20 + n - 1 with 12 candidate ticks in
+    front: 52 x 67 = 3484 groups (per = 4, threads 871 and up own nothing) and 17 x 67 = 1139 (per = 2, the last owning
+    thread's run is cut short by n_groups, 454 threads own nothing)."""
+    E67, cap = 67, 64
+    tr = S.make_trajectory(60, E=E67, K=cap, seed=4)
+    b = batch(cap, False, E67)
+    got, want = run_both(b, tr, 20, n, 0)
+    offsets = _np(b._nstep_last[2]).astype(np.int64)
+    b.synchronize()
+    M = check(got, want)
+    n_groups = (12 + n) * E67 * cap // 64
+    per = (n_groups + 1023) // 1024
+    owners = (n_groups + per - 1) // per
+    print("n_ticks %d: %d groups, per %d, %d threads without a group, %d records" % (n, n_groups, per, 1024 - owners, M))
+    assert offsets.shape == (n_groups + 1,)
+    assert per >= 2 and owners < 1024 and (n_groups % per != 0) == ragged
+    counts = (got[4] != 0).reshape(n_groups, 64).sum(axis=1)
+    assert counts.max() > 1 and (counts == 0).any() and M > 1024
+    assert np.array_equal(offsets[:-1], np.cumsum(counts) - counts) and offsets[n_groups] == M == int(got[2])
 
 
 # ------------------------------------------------------------------ 2. the cut-off
