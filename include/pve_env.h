@@ -132,7 +132,12 @@ typedef struct pve_env_info {
     int32_t veh_rec[PVE_LANES];          /* ref :207 */
     int32_t id_seq, passed_veh, passed_veh_step_total;   /* ref :197-198, 212 */
     int32_t head_valid[PVE_MAX_DIRS], head_lane[PVE_MAX_DIRS], head_j[PVE_MAX_DIRS];  /* virtual_lane_4[d][0][1:3], ref :1517 */
-    int32_t overflow;                    /* spawns deferred because the env was full */
+    int32_t overflow;                    /* spawns deferred because the env was full: one per lane and tick.  The rule (fused and split
+                                            ticks, every kernel): room = capacity - (vehicles alive when the tick starts) -- the vehicles
+                                            this tick deletes free their slots for the NEXT tick only; when more lanes are due than
+                                            there is room, the lowest lane indices spawn; a deferred lane keeps its cursor (veh_rec),
+                                            takes no id (id_seq) and no intention (intention_re, the 8-lane draw) and is due again on
+                                            the next tick */
     int32_t intention_re;                /* ref :42, :387-392 (lane_num 4 / 8) */
 } pve_env_info;
 

@@ -53,6 +53,13 @@ def lib():
     for name in ("pvo_reward", "pvo_state", "pvo_jerks"):
         getattr(L, name).restype = dp
         getattr(L, name).argtypes = [vp]
+    L.pvo_set_capacity.restype = C.c_int
+    L.pvo_set_capacity.argtypes = [vp, C.c_int]
+    for name in ("pvo_overflow", "pvo_tick_deferred"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp]
+    L.pvo_deferred_lanes.restype = C.c_uint
+    L.pvo_deferred_lanes.argtypes = [vp]
     L.pvo_time.restype = C.c_double
     L.pvo_time.argtypes = [vp]
     L.pvo_lane_counts.argtypes = [vp, ip]
@@ -80,9 +87,13 @@ def _arr(ptr, n, dtype):
 
 class OracleEnv:
     """Single environment; same call protocol as the reference object
-    (ctor warm-up, step, scene_update, delete_vehicle)."""
+    (ctor warm-up, step, scene_update, delete_vehicle).
+    capacity: the slots of a batched env.  None = unbounded, as the reference.  Otherwise a spawn is deferred when the
+    intersection is full: room = capacity - (vehicles alive at tick start) -- this tick's deletions free nothing until the
+    next tick -- the lowest due lanes are granted, a deferred lane keeps its cursor, id and everything else and is due
+    again on the next tick; `overflow` counts the deferred lanes of every tick."""
 
-    def __init__(self, arrive_time, **params):
+    def __init__(self, arrive_time, capacity=None, **params):
         L = lib()
         self._L = L
         prm = PvoParams()
@@ -95,6 +106,9 @@ class OracleEnv:
         assert arr.ndim == 2 and arr.shape[1] == 12
         self._arr = arr
         self._h = L.pvo_create(arr.ctypes.data_as(C.POINTER(C.c_double)), arr.shape[0], C.byref(prm), 0)
+        self.capacity = None if capacity is None else int(capacity)
+        if capacity is not None and L.pvo_set_capacity(self._h, int(capacity)) != 0:
+            raise ValueError("capacity must be at least one slot per lane")
         self.tick_no = 0
 
     def __del__(self):
@@ -120,6 +134,11 @@ class OracleEnv:
     @property
     def current_time(self):
         return self._L.pvo_time(self._h)
+
+    @property
+    def overflow(self):
+        """spawns deferred so far, one per lane and tick (0 for an unbounded env)"""
+        return self._L.pvo_overflow(self._h)
 
     @property
     def ref_would_raise(self):
@@ -194,6 +213,9 @@ class OracleEnv:
         ev = np.zeros(63, np.int32)
         L.pvo_export_env(h, ev.ctypes.data_as(C.POINTER(C.c_int)))
         rec["id_seq"], rec["passed"], rec["passed_step_total"] = int(ev[0]), int(ev[1]), int(ev[2])
+        # capacity bound: deferrals so far / of this tick / this tick's deferred lanes as a mask (all 0 when unbounded)
+        rec["overflow"], rec["deferred"] = L.pvo_overflow(h), L.pvo_tick_deferred(h)
+        rec["deferred_lanes"] = int(L.pvo_deferred_lanes(h))
         rec["veh_num"] = ev[3:15].copy()
         rec["veh_rec"] = ev[15:27].copy()
         rec["heads"] = ev[27:63].reshape(12, 3).copy()

@@ -53,6 +53,13 @@ def lib():
     for name in ("pvg_reward", "pvg_state", "pvg_jerks"):
         getattr(L, name).restype = dp
         getattr(L, name).argtypes = [vp]
+    L.pvg_set_capacity.restype = C.c_int
+    L.pvg_set_capacity.argtypes = [vp, C.c_int]
+    for name in ("pvg_overflow", "pvg_tick_deferred"):
+        getattr(L, name).restype = C.c_int
+        getattr(L, name).argtypes = [vp]
+    L.pvg_deferred_lanes.restype = C.c_uint
+    L.pvg_deferred_lanes.argtypes = [vp]
     L.pvg_time.restype = C.c_double
     L.pvg_time.argtypes = [vp]
     L.pvg_export_vehicles.argtypes = [vp, ip, dp, dp, ip]
@@ -74,9 +81,11 @@ def _arr(ptr, n, dtype):
 
 class OracleGeoEnv:
     """Single environment of `lane_num` physical lanes; same call protocol as the reference object.
-    `choice` ([rows, lane_num] of 0/1) replaces the reference's random.randint(0, 1) draws (8-lane)."""
+    `choice` ([rows, lane_num] of 0/1) replaces the reference's random.randint(0, 1) draws (8-lane).
+    capacity: the slots of a batched env (None = unbounded, as the reference); the deferral rule of OracleEnv.  A deferred
+    spawn draws no intention: `intention_re` and the 8-lane `choice` cursor stay where they are."""
 
-    def __init__(self, arrive_time, lane_num, choice=None, **params):
+    def __init__(self, arrive_time, lane_num, choice=None, capacity=None, **params):
         L = lib()
         self._L = L
         prm = PvgParams()
@@ -98,6 +107,9 @@ class OracleGeoEnv:
                                arr.shape[0], self.lane_num, C.byref(prm))
         if not self._h:
             raise ValueError("lane_num must be 4, 8 or 12")
+        self.capacity = None if capacity is None else int(capacity)
+        if capacity is not None and L.pvg_set_capacity(self._h, int(capacity)) != 0:
+            raise ValueError("capacity must be at least one slot per lane")
         self.tick_no = 0
 
     def __del__(self):
@@ -121,6 +133,11 @@ class OracleGeoEnv:
     @property
     def current_time(self):
         return self._L.pvg_time(self._h)
+
+    @property
+    def overflow(self):
+        """spawns deferred so far, one per lane and tick (0 for an unbounded env)"""
+        return self._L.pvg_overflow(self._h)
 
     @property
     def ref_would_raise(self):
@@ -186,6 +203,9 @@ class OracleGeoEnv:
         ev = np.zeros(4 + 2 * nl + 3 * nd_, np.int32)
         L.pvg_export_env(h, ev.ctypes.data_as(C.POINTER(C.c_int)))
         rec["id_seq"], rec["passed"], rec["passed_step_total"] = int(ev[0]), int(ev[1]), int(ev[2])
+        # capacity bound: deferrals so far / of this tick / this tick's deferred lanes as a mask (all 0 when unbounded)
+        rec["overflow"], rec["deferred"] = L.pvg_overflow(h), L.pvg_tick_deferred(h)
+        rec["deferred_lanes"] = int(L.pvg_deferred_lanes(h))
         rec["intention_re"] = int(ev[3])
         rec["veh_num"] = ev[4:4 + nl].copy()
         rec["veh_rec"] = ev[4 + nl:4 + 2 * nl].copy()

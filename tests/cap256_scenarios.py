@@ -47,6 +47,24 @@ def check_dense_split(backend, env, ticks=DENSE_TICKS):
     return b
 
 
+# The full scenario: the same stream seed at 5000 veh/h/lane with the braking tape fills all 256 slots (env 0: from tick 265 on,
+# 464 deferred spawns in 350 ticks, 61 collisions, 198 dead-locks on the oracle side).
+FULL_RATE = 5000.0
+
+
+def full_case(env, ticks=DENSE_TICKS):
+    arr = synthetic_arrivals(env + 1, rate=FULL_RATE, horizon_s=DENSE_TICKS * 0.1 + 30.0, seed=DENSE_SEED)[env]
+    return types.SimpleNamespace(name="full256_e%d" % env, arrive=np.ascontiguousarray(arr), ctor={}, ticks=ticks, policy=brake_policy)
+
+
+def check_full_split(backend, env=0, ticks=DENSE_TICKS):
+    """Split protocol at 256 slots through a FULL intersection against the capacity-bound oracle: every tick, every field at
+    1e-9, the grants / cursors / id counter / deferral count every tick, metrics()["overflow"] == the oracle's count > 0."""
+    b = scenarios.check_split_vs_oracle(full_case(env, ticks), backend, ticks, capacity=256, tol=1e-9, bounded=True)
+    assert b.metrics()["overflow"] > 0
+    return b
+
+
 def check_dense_fused(backend, env, ticks=DENSE_TICKS):
     scenarios.check_fused_equals_split(dense_case(env, ticks), backend, ticks, capacity=256)
 

@@ -12,7 +12,8 @@ entries under the names metrics() uses:
   passed, passed_steps   the last passed / passed_step_total
   collided       sum of count(coll_pv > 0): main.py:410-412 (tests/golden/gen_golden.py), not the 9-tuple's `collisions`
   locks          sum of lock
-  overflow       0 (the reference never defers a spawn)
+  overflow       sum of the tick's deferral count (`deferred`) of a capacity-bound oracle's records; 0 for unbounded records and
+                 for digest rows (the reference never defers a spawn)
   sum_reward     math.fsum of every reward of every tick
   sum_jerk       math.fsum of every `jerks` entry
 
@@ -42,7 +43,7 @@ class MetricsRef:
     def __init__(self, capacity):
         self.capacity = int(capacity)
         self.ticks = self.alive_steps = self.ctl_steps = self.collided = self.locks = 0
-        self.spawned = self.passed = self.passed_steps = 0
+        self.spawned = self.passed = self.passed_steps = self.overflow = 0
         self.collided_known = True                # (a digest row carries no coll_pv)
         self._rewards, self._jerks = [], []       # every term (records), or one partial sum per tick (digest rows)
         self.reward_scale = self.jerk_scale = 0.0  # sum of max(1, |term|)
@@ -55,6 +56,7 @@ class MetricsRef:
         self.ctl_steps += len(rec["ids"])
         self.collided += sum(1 for c in rec["coll_pv"] if c > 0)
         self.locks += int(rec["lock"])
+        self.overflow += int(rec.get("deferred", 0))     # (a capacity-bound oracle: the lanes it deferred this tick)
         self.spawned, self.passed, self.passed_steps = int(rec["id_seq"]), int(rec["passed"]), int(rec["passed_step_total"])
         for x in rec["reward"]:
             self._rewards.append(float(x)); self.reward_scale += max(1.0, abs(float(x)))
@@ -80,7 +82,7 @@ class MetricsRef:
     def as_dict(self):
         d = dict(ticks=self.ticks, slot_steps=self.ticks * self.capacity, alive_steps=self.alive_steps,
                  ctl_steps=self.ctl_steps, spawned=self.spawned, passed=self.passed, passed_steps=self.passed_steps,
-                 collided=self.collided, locks=self.locks, overflow=0,
+                 collided=self.collided, locks=self.locks, overflow=self.overflow,
                  sum_reward=math.fsum(self._rewards), sum_jerk=math.fsum(self._jerks))
         if not self.collided_known:
             del d["collided"]

@@ -62,6 +62,17 @@ SPECS = {s.name: s for s in [
 ]}
 
 
+# Full intersections: bursts that want more slots than the capacity has.  The oracles of these run capacity-bound (the deferral
+# rule of ph_final, pinned to the reference by tests/test_oracle_bounded.py), the accumulators take every tick's deferral count
+# from their records; once the streams are dry the lanes that were kept waiting drain.  One per kernel family.
+FULL_SPECS = {s.name: s for s in [
+    Spec("l12_c64_full", 12, 64, [(0.5, 9.0, 41), (0.8, 8.0, 42)], (150, 7, 243), "rand3", {}),
+    Spec("l12_c128_full", 12, 128, [(0.3, 12.0, 45), (0.4, 12.0, 46)], (150, 7, 243), "rand3", {}),       # (the HOME build's width)
+    Spec("l4_c64_full", 4, 64, [(0.2, 9.0, 43)], (150, 7, 243), "rand3", {}),
+    Spec("l8_c64_full", 8, 64, [(0.4, 9.0, 44)], (150, 7, 243), "rand3", {}),
+]}
+
+
 def spec_cfg(spec):
     return _ctor_of(spec.cfg) if isinstance(spec.cfg, str) else dict(spec.cfg)
 
@@ -124,7 +135,8 @@ def reference(name):
     (snaps[t] = the batch's vector after t ticks, env_snaps[t] = one per intersection) and the reach statistics."""
     if name in _refs:
         return _refs[name]
-    spec = SPECS[name]
+    bounded = name in FULL_SPECS
+    spec = FULL_SPECS[name] if bounded else SPECS[name]
     cfg = spec_cfg(spec)
     E, K, L, T = len(spec.envs), spec.capacity, spec.lane_num, sum(spec.calls)
     streams = [burst_arrivals(L, g, d, s) for g, d, s in spec.envs]
@@ -134,7 +146,8 @@ def reference(name):
         arr[e, :len(a)] = a
     choice = synthetic_intentions(E, rows, seed=spec.envs[0][2], lane_num=8) if L == 8 else None
     pol = get_policy(spec.tape)
-    oracles = [make_oracle(arr[e], L, choice=None if choice is None else choice[e], **cfg) for e in range(E)]
+    oracles = [make_oracle(arr[e], L, choice=None if choice is None else choice[e], **(dict(cfg, capacity=K) if bounded else cfg))
+               for e in range(E)]
     accs = [metrics_ref.MetricsRef(K) for _ in range(E)]
     stats = [TickStats(K) for _ in range(E)]
     actions = np.zeros((T, E, K))
@@ -154,6 +167,10 @@ def reference(name):
         if t + 1 in cuts:
             env_snaps[t + 1] = [a.snapshot() for a in accs]
             snaps[t + 1] = metrics_ref.total(env_snaps[t + 1])
+    if bounded:             # every intersection defers spawns, and still does in the last segment (every snapshot moves)
+        cut = sorted(cuts)
+        assert all(s[0]["overflow"] > 0 for s in env_snaps[cut[0]]), "%s: an intersection never defers a spawn" % name
+        assert snaps[T][0]["overflow"] > snaps[cut[1]][0]["overflow"] > snaps[cut[0]][0]["overflow"], name
     n_ids = max(int(s[0]["spawned"]) for s in env_snaps[T]) + 1
     table = np.stack([pol(t, np.arange(n_ids), np.ones(n_ids, np.int32)) for t in range(T)])
     ref = Reference(spec, arr, choice, actions, table, snaps, env_snaps, [s.summary() for s in stats], cfg,

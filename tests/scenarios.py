@@ -11,8 +11,25 @@ STATE_F = ("p", "v", "a", "jerk", "jerk_sum", "vir_dis", "closer_p")
 STATE_I = ("id", "seq", "vnum", "step", "count", "meta", "hdr")
 
 
-def check_split_vs_oracle(case, backend, ticks, capacity=128, tol=1e-9):
-    orc = OracleEnv(case.arrive, **case.ctor)
+def _bounded_tick_checks(rec, id_seq_pre, eo, info, lane_num, what):
+    """bounded mode: what a deferred spawn must leave alone, per tick, from the oracle's record: the grants (env_out N_SPAWNED), the
+    population after the fused tick (N_POST; eo=None: after pve_compact, from read_env alone), and read_env's id counter, spawn
+    cursors, deferral count and intention counter."""
+    n_post = len(rec["veh_i"]) - len(rec["deleted"])
+    if eo is not None:
+        assert int(eo[6]) == rec["id_seq"] - id_seq_pre, "%s: N_SPAWNED %d, the oracle granted %d" % (what, eo[6], rec["id_seq"] - id_seq_pre)
+        assert int(eo[7]) == n_post, what + ": N_POST"
+    assert info.n_alive == n_post, what + ": n_alive"
+    assert info.id_seq == rec["id_seq"] and list(info.veh_rec)[:lane_num] == rec["veh_rec"].tolist(), what + ": id_seq / veh_rec"
+    assert info.overflow == rec["overflow"], "%s: overflow %d, the oracle deferred %d" % (what, info.overflow, rec["overflow"])
+    if lane_num != 12:
+        assert info.intention_re == rec["intention_re"], what + ": intention_re"
+
+
+def check_split_vs_oracle(case, backend, ticks, capacity=128, tol=1e-9, bounded=False):
+    """bounded=True: the oracle defers spawns as a batched env of `capacity` slots does (OracleEnv(capacity=)): the comparison goes
+    on through a full intersection, and metrics()["overflow"] must equal the oracle's count instead of 0."""
+    orc = OracleEnv(case.arrive, capacity=capacity if bounded else None, **case.ctor)
     b = make_batch(case.arrive, 1, capacity, backend, **case.ctor)
     env = SplitEnv(b)
     for t in range(min(ticks, case.ticks)):
@@ -21,8 +38,12 @@ def check_split_vs_oracle(case, backend, ticks, capacity=128, tol=1e-9):
         assert np.array_equal(va, vb) and np.array_equal(ca, cb), "alive set differs at tick %d" % t
         assert close(np.where(ca[:, None] != 0, oa, 0), ob, tol), "stored observation differs at tick %d" % t
         acts = case.policy(t, va, ca, oa)
-        compare_records(orc.tick(acts), env.tick(acts), tol=tol, label=case.name)
-    assert b.metrics()["overflow"] == 0
+        id_seq_pre = orc.snapshot()["id_seq"] if bounded else 0
+        ra = orc.tick(acts)
+        compare_records(ra, env.tick(acts), tol=tol, label=case.name)
+        if bounded:                 # (env_out's N_SPAWNED / N_POST of the split call: bounded_scenarios.check_split_bounded)
+            _bounded_tick_checks(ra, id_seq_pre, None, b.read_env(0), 12, "%s tick %d" % (case.name, t))
+    assert b.metrics()["overflow"] == (orc.overflow if bounded else 0)
     return b
 
 
@@ -151,20 +172,6 @@ def check_empty_and_exhausted(backend):
     assert info.n_alive == orc.n_alive and info.passed_veh == 2
 
 
-class CapacityOverflow(Exception):
-    """The workload filled every slot of an intersection: the batched env defers the spawn (documented deviation,
-    counted in metrics()['overflow']), the reference / oracle does not -- the comparison ends there."""
-
-
-def _overflow_guard(b, fn):
-    try:
-        fn()
-    except (AssertionError, ValueError) as ex:
-        if b.metrics()["overflow"] > 0:
-            raise CapacityOverflow(str(ex))
-        raise
-
-
 def symmetric_arrivals(n_envs, gap_s, rows, lane_groups, lane_num=12):
     """Arrival streams in which the lanes of a group spawn in the SAME tick (identical arrival times): while nobody steers
     them apart, vehicles of symmetric lanes keep identical positions, i.e. identical virtual distances in every list they
@@ -178,16 +185,20 @@ def symmetric_arrivals(n_envs, gap_s, rows, lane_groups, lane_num=12):
     return out
 
 
-def check_fuzz_vs_oracle(backend, n_envs, capacity, ticks, rate, seed, action_scale=3.0, quantize=None, arrivals=None):
+def check_fuzz_vs_oracle(backend, n_envs, capacity, ticks, rate, seed, action_scale=3.0, quantize=None, arrivals=None, bounded=False):
     """Random action tapes (uniform in [-scale, scale], optionally quantised to provoke exact ties), every env
     compared with its own oracle every tick: controlled set, rewards, collision counters, lock counts, and the
-    full persistent state at the end. Exercises vd ties, long dead-lock cycles, collisions, mid-lane deletions."""
+    full persistent state at the end. Exercises vd ties, long dead-lock cycles, collisions, mid-lane deletions.
+    bounded=False: the oracles spawn without limit, as the reference: the workload must never fill an intersection (overflow == 0).
+    bounded=True: the oracles defer spawns by the batch's capacity (OracleEnv(capacity=)): the comparison goes on through full
+    intersections, with the grants, cursors, id counter and deferral count checked every tick and metrics()["overflow"] equal to
+    the oracles' count at the end."""
     rng = np.random.default_rng(seed)
     arr = arrivals if arrivals is not None else synthetic_arrivals(n_envs, rate=rate, horizon_s=ticks * 0.1 + 30, seed=seed)
     b = make_batch(arr, n_envs, capacity, backend, outputs=("obs_post", "obs_pre", "reward", "flags", "nbr",
                                                             "env_out", "new_slot", "lanej"))
     b.reset()
-    oracles = [OracleEnv(arr[e]) for e in range(n_envs)]
+    oracles = [OracleEnv(arr[e], capacity=capacity if bounded else None) for e in range(n_envs)]
     tot_coll = tot_lock = 0
     check_fuzz_vs_oracle.max_ctl = 0          # (most controlled vehicles any env held: the dense mapping's second wave)
     def run_ticks():
@@ -202,7 +213,10 @@ def check_fuzz_vs_oracle(backend, n_envs, capacity, ticks, rate, seed, action_sc
             for e, o in enumerate(oracles):
                 n = o.n_alive
                 _vid, ctlm, _ = o.alive_view()
+                id_seq_pre = o.snapshot()["id_seq"] if bounded else 0
                 rec = o.tick(np.where(ctlm != 0, acts[e, :n], 0.0))
+                if bounded:
+                    _bounded_tick_checks(rec, id_seq_pre, eo[e], b.read_env(e), 12, "tick %d env %d" % (t, e))
                 ctl = (flags[e, :n] & 2) != 0
                 check_fuzz_vs_oracle.max_ctl = max(check_fuzz_vs_oracle.max_ctl, int(ctl.sum()))
                 assert int(eo[e, 0]) == n and int(ctl.sum()) == len(rec["ids"]), "controlled set: tick %d env %d" % (t, e)
@@ -215,13 +229,14 @@ def check_fuzz_vs_oracle(backend, n_envs, capacity, ticks, rate, seed, action_sc
                 assert close(rec["obs0"], obs[e, :n][ctl], 1e-9), "obs: tick %d env %d" % (t, e)
                 tot_coll += rec["collisions"]
                 tot_lock += rec["lock"]
-    _overflow_guard(b, run_ticks)
+    run_ticks()
     for e, o in enumerate(oracles):
         info, vi, vf = state_snapshot(b, e)
         ovi, ovf, _ = o.vehicles()
         assert np.array_equal(vi[:, :13], ovi[:, :13]), "final state ints, env %d" % e
         assert close(ovf[:, :5], vf[:, :5], 1e-9), "final state floats, env %d" % e
-    assert b.metrics()["overflow"] == 0
+    assert b.metrics()["overflow"] == (sum(o.overflow for o in oracles) if bounded else 0)
+    check_fuzz_vs_oracle.overflow = int(b.metrics()["overflow"])
     return tot_coll, tot_lock
 
 
@@ -314,11 +329,12 @@ def check_general_path_equals_fast_path(backend, n_envs=6, capacity=128, ticks=3
 
 
 def check_geo_fuzz_vs_oracle(backend, lane_num, n_envs, capacity, ticks, rate, seed, action_scale=3.0, quantize=None,
-                             arrivals=None, cfg=None):
+                             arrivals=None, cfg=None, bounded=False):
     """Random action tapes on a batch of 4- or 8-lane envs (own arrival + intention streams), fused ticks, every env
     against its own sequential oracle every tick: processing order, controlled set, neighbours, rewards,
     observations, collision counters, lock counts; full persistent state at the end.
-    cfg: constructor arguments (vm, dis_ctl, lane_cw, ...: ref :21-23) for every batch and every oracle."""
+    cfg: constructor arguments (vm, dis_ctl, lane_cw, ...: ref :21-23) for every batch and every oracle.
+    bounded: as check_fuzz_vs_oracle (a deferred spawn also draws no intention: intention_re every tick)."""
     cfg = cfg or {}
     from oracle.oracle_geo import OracleGeoEnv
     from pve_mcc_amd.arrivals import synthetic_intentions
@@ -329,7 +345,8 @@ def check_geo_fuzz_vs_oracle(backend, lane_num, n_envs, capacity, ticks, rate, s
     b = make_batch(arr, n_envs, capacity, backend, lane_num=lane_num, intentions=ch,
                    outputs=("obs_post", "obs_pre", "reward", "flags", "nbr", "env_out", "new_slot", "lanej"), **cfg)
     b.reset()
-    oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e], **cfg) for e in range(n_envs)]
+    oracles = [OracleGeoEnv(arr[e], lane_num, choice=None if ch is None else ch[e], capacity=capacity if bounded else None, **cfg)
+               for e in range(n_envs)]
     tot_coll = tot_lock = 0
     def run_ticks():
         nonlocal tot_coll, tot_lock
@@ -343,7 +360,10 @@ def check_geo_fuzz_vs_oracle(backend, lane_num, n_envs, capacity, ticks, rate, s
             for e, o in enumerate(oracles):
                 n = o.n_alive
                 _vid, ctlm, _ = o.alive_view()
+                id_seq_pre = o.snapshot()["id_seq"] if bounded else 0
                 rec = o.tick(np.where(ctlm != 0, acts[e, :n], 0.0))
+                if bounded:
+                    _bounded_tick_checks(rec, id_seq_pre, eo[e], b.read_env(e), lane_num, "tick %d env %d" % (t, e))
                 f = flags[e, :n]
                 order = np.lexsort((lanej[e, :n] & 0xFFFF, (f >> 6) & 3, lanej[e, :n] >> 16))
                 ctl = order[((f & 2) != 0)[order]]
@@ -359,7 +379,7 @@ def check_geo_fuzz_vs_oracle(backend, lane_num, n_envs, capacity, ticks, rate, s
                 assert close(rec["obs0"], obs[e, ctl], 1e-9), "obs: tick %d env %d" % (t, e)
                 tot_coll += rec["collisions"]
                 tot_lock += rec["lock"]
-    _overflow_guard(b, run_ticks)
+    run_ticks()
     for e, o in enumerate(oracles):
         info, vi, vf = state_snapshot(b, e)
         ovi, ovf, _, ointent = o.vehicles()
@@ -367,7 +387,8 @@ def check_geo_fuzz_vs_oracle(backend, lane_num, n_envs, capacity, ticks, rate, s
         assert close(ovf[:, :5], vf[:, :5], 1e-9), "final state floats, env %d" % e
         got = np.array([[v.intention, v.route] for v in b.read_vehicles(e)], np.int32).reshape(-1, 2)
         assert np.array_equal(got, ointent), "intentions / routes, env %d" % e
-    assert b.metrics()["overflow"] == 0
+    assert b.metrics()["overflow"] == (sum(o.overflow for o in oracles) if bounded else 0)
+    check_geo_fuzz_vs_oracle.overflow = int(b.metrics()["overflow"])
     return tot_coll, tot_lock
 
 

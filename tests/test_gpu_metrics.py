@@ -29,6 +29,16 @@ def test_gpu_tick_metrics(name, form):
     S.check_open_loop(BACKEND, name, form)
 
 
+# ------------------------------------------------------------------ full intersections: `overflow` against capacity-bound oracles
+@pytest.mark.parametrize("form,kw", [("step", {}), ("split", {}), ("pool", dict(launch="resident")), ("pool", dict(chunk=7, **QUEUE)),
+                                     ("table", dict(chunk=1, **QUEUE))])
+@pytest.mark.parametrize("name", sorted(S.FULL_SPECS))
+def test_gpu_metrics_full_intersections(name, form, kw):
+    """overflowing bursts, one per kernel family (12 lanes at 64 slots and at the HOME build's 128, 4 lanes, 8 lanes): all twelve
+    sums through the deferred spawns, `overflow` = the bounded oracles' deferral counts, the float sums at their usual bars"""
+    S.check_open_loop(BACKEND, name, form, **kw)
+
+
 def test_gpu_tick_metrics_float32_rows():
     S.check_open_loop(BACKEND, "l12_c128", "step", obs_dtype=torch.float32)
 

@@ -140,6 +140,19 @@ def test_emulated_metrics_match_the_accumulator(name, form, kw):
 
 
 @pytest.mark.parametrize("form,kw", FORMS)
+@pytest.mark.parametrize("name", sorted(S.FULL_SPECS))
+def test_emulated_metrics_full_intersections(name, form, kw):
+    """overflowing bursts: `overflow` (and every other sum, through the deferred spawns) against capacity-bound oracles"""
+    S.check_open_loop(BACKEND, name, form, **kw)
+
+
+def test_emulated_metrics_full_intersection_home_block(monkeypatch):
+    monkeypatch.setenv("PVE_EMU_HOME", "1")
+    for source in ("pool", "table"):
+        S.check_open_loop(BACKEND, "l12_c128_full", source, chunk=7, persistent=True, launch="persistent")
+
+
+@pytest.mark.parametrize("form,kw", FORMS)
 def test_emulated_metrics_match_the_accumulator_256(wide, form, kw):
     S.check_open_loop(BACKEND, "l12_c256", form, **kw)
 
