@@ -313,7 +313,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 //    cores then deliver h - mean(h) directly and LayerNorm's mean pass (sum, exchange, 64 subtractions) disappears;
 //  * a vehicle lives in 2 lanes instead of 4: one v_permlane32_swap per LayerNorm sum instead of two exchanges;
 //  * 1 / sqrt(var + eps) is v_rsq_f32, 3 tanh(z) = 3 - 6 / (exp(2 z) + 1) with v_exp_f32 / v_rcp_f32 (1 ulp each; measured
-//    3.6e-7 absolute on the action), divisions by the layer widths are multiplications;
+//    3.6e-7 absolute on the actions of a roll-out, 8.1e-7 over z in [-20, 20]: tests/test_gpu_math_probe.py), divisions by
+//    the layer widths are multiplications;
 //  * every weight is centered, split and laid out in A-operand order ONCE (k_actor_pack, pve_set_actor) instead of by
 //    every workgroup of every launch.
 // The same device function (`actor_tile32`) is called by the stand-alone kernel k_actor_h (weights staged in LDS by persistent

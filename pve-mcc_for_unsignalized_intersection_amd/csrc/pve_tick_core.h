@@ -771,8 +771,9 @@ PVE_HD bool key_less(double d1, double v1, int r1, double d2, double v2, int r2)
 
 // x / b for a constant b with rb = RN(1 / b): q = RN(x rb), r = x - q b (exact in one FMA), q' = RN(q + r rb) is the
 // correctly rounded quotient (Markstein 1990), i.e. bit for bit what the division instruction sequence returns, in 3
-// instructions instead of ~13 incl. a quarter-rate reciprocal.  Checked against IEEE division on 4.9e9 operands (random
-// over 128 binades + every neighbour of the rounding midpoints) for b = 3, 6 and nine other divisors: identical except for
+// instructions instead of ~13 incl. a quarter-rate reciprocal.  Held to IEEE division by tests/test_math_probe.py and
+// tests/test_gpu_math_probe.py (random over 128 binades, brake_needed's operands, the neighbours of the rounding midpoints;
+// b = |am|, 2 |am| of every tested configuration): identical except for
 // the sign of a zero result and results in the subnormal range, neither of which can reach a decision here (the terms are
 // 0 or >= 1e-14 in magnitude, and d_safe is only compared); pve_create refuses |am| outside [1e-6, 1e6].
 PVE_HD double div_const(double x, double b, double rb)
