@@ -28,10 +28,12 @@ using namespace pve;
 // environment variable on its launch path.
 #ifdef PVE_AB_KNOBS
 #define PVE_KNOB(name_) getenv(name_)
+static constexpr bool knobs_built = true;
 #else
 #define PVE_KNOB(name_) ((const char *)nullptr)
+static constexpr bool knobs_built = false;
 #endif
-// the HOME build of the persistent table-source kernel (k_rollout<128, 5, ..>, 10 workgroups per CU) is what launch_rollout
+// the HOME build of the persistent table-source kernel (k_rollout<128, 5, ..>, 10 workgroups per CU) is what pick_rollout
 // takes when it is eligible; -DPVE_HOME_DEFAULT=0 builds a library that keeps the 8-workgroup kernel (A/B)
 #ifndef PVE_HOME_DEFAULT
 #define PVE_HOME_DEFAULT 1
@@ -1003,38 +1005,84 @@ template <typename K> static hipError_t resident_blocks(int *nb, K kernel, int t
     return hipSuccess;
 }
 
-// Resident workgroups of the persistent roll-out kernels, per DEVICE (a process may hold handles on several GPUs, and they
-// need not be the same part): [device][kernel family (12-lane / general geometry)][capacity 64 / 128 / 256] workgroups per CU + the
-// CU count, filled by the first persistent launch on that device.
-struct OccCache {
-    static constexpr int MAX_DEV = 64;
-    std::mutex mu;
-    int wgs[MAX_DEV][4][3] = {};       // family: 0 = k_rollout, 1 = k_rollout_geo, 2 = k_rollout_geo with the actor, 3 = k_rollout<128, 5, ..> (HOME)
-    int n_cu[MAX_DEV] = {};
-    // -> workgroups the device holds at once for (family, cap), or -1 (err set); `query` = the occupancy call of the variant
-    template <typename Q>
-    long long resident(int family, int cap, Q query, std::string &err)
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) { err = "hipGetDevice failed"; return -1; }
-        const int ci = cap == 64 ? 0 : (cap == 128 ? 1 : 2);
-        std::lock_guard<std::mutex> lock(mu);
-        const bool cached = dev >= 0 && dev < MAX_DEV && wgs[dev][family][ci] > 0;
-        int nb = cached ? wgs[dev][family][ci] : 0, cus = cached ? n_cu[dev] : 0;
-        if (!cached) {
-            hipDeviceProp_t prop;
-            const hipError_t e = query(&nb);
-            if (e != hipSuccess || nb <= 0 || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-                err = std::string("occupancy query of the persistent roll-out: ") + hipGetErrorString(e);
-                return -1;
-            }
-            cus = prop.multiProcessorCount;
-            if (dev >= 0 && dev < MAX_DEV) { wgs[dev][family][ci] = nb; n_cu[dev] = cus; }
-        }
-        return (long long)nb * cus;
-    }
+// ------------------------------------------------------------------ run-time configuration -> kernel variant
+// with_flags(f, a, b, ..) hands run-time booleans to f as compile-time constants: f(std::bool_constant<a>{}, std::bool_constant<b>{}, ..).
+// (The capacity goes through Backend::with_cap.)  Every combination of the flags is compiled: a launcher instantiates only the
+// variants its family declares (`exists` below).
+template <typename F> static int with_flags(F f) { return f(); }
+template <typename F, typename... Bs> static int with_flags(F f, bool b, Bs... rest)
+{
+    return b ? with_flags([&](auto... r) { return f(std::true_type{}, r...); }, rest...)
+             : with_flags([&](auto... r) { return f(std::false_type{}, r...); }, rest...);
+}
+
+// The variants of k_rollout the library holds: `exists` names them (a launcher instantiates nothing else), `sized_by` is the kernel
+// whose occupancy sizes the persistent grid, and kernel() is the only place in the host code that writes k_rollout<..> with
+// arguments (tools/probe_kernel.sh's instantiation aside).
+template <int CAP_, int WPE_, bool PROF_, bool ACT_, bool TRAIN_, bool IDT_, bool PERS_> struct Rollout12 {
+    static constexpr int CAP = CAP_;
+    static constexpr bool PERS = PERS_, exists =
+        !(PERS_ && PROF_) && !(ACT_ && IDT_) &&                                       // (the kernel's own static_asserts)
+        (WPE_ == 4 ? !PROF_ || (CAP_ <= 128 && !ACT_ && !TRAIN_ && !IDT_)            // the phase-cycle diagnostics: the default kernel at 64 / 128 slots
+                   : WPE_ == 5 && CAP_ == 128 && PERS_ && !ACT_ && !TRAIN_);          // HOME: 128 slots, the queue form, zero / pool / table
+    // as many workgroups as the chip holds at once of the capacity's default queue kernel (each capacity from its own kernel's
+    // occupancy: the 256-slot block admits half the 128-slot workgroups per CU); HOME: of its table kernel.  The TRAIN and IDT
+    // variants have the default's block.  The ACT variants do not: at 64 slots k_rollout<64, 4, false, true, .., true> has
+    // 12 368 B of LDS against the default's 10 240 B -- by the compiler's tables and resident_blocks' granule rule 12 resident
+    // workgroups per CU where the grid is sized for 16 (at 128 and 256 slots both come out equal, 8 and 4).  Derived, not
+    // measured.
+    typedef Rollout12<CAP_, WPE_, false, false, false, WPE_ == 5, true> sized_by;
+    static auto kernel() { return k_rollout<CAP_, WPE_, PROF_, ACT_, TRAIN_, IDT_, PERS_>; }
 };
-static OccCache g_occ;
+
+// ... and of k_rollout_geo, which takes its arguments in another order: layout x capacity x {default, training outputs, id-indexed
+// table, actor, actor + training outputs} x launch form
+template <int CAP_, bool FIX4_, int WPE_, bool TRAIN_, bool IDT_, bool PERS_, bool ACT_> struct RolloutGeo {
+    static constexpr int CAP = CAP_;
+    static constexpr bool PERS = PERS_, exists =
+        !(TRAIN_ && IDT_) && !(ACT_ && IDT_) &&                                       // (the kernel's own static_asserts)
+        CAP_ <= 128 && !(PERS_ && TRAIN_ && ACT_) &&                                  // (the 4- / 8-lane layouts: 64 or 128 slots)
+        (WPE_ == 4 || (knobs_built && WPE_ == 5 && CAP_ == 128 && !FIX4_ && !TRAIN_ && !IDT_ && !PERS_ && !ACT_));   // (PVE_ROLLOUT_GEO_WPE5)
+    // (the variants of one capacity share their register budget; the actor's parameters add 2 KB of LDS: a query of its own)
+    typedef RolloutGeo<CAP_, true, 4, false, false, true, ACT_> sized_by;
+    static auto kernel() { return k_rollout_geo<CAP_, FIX4_, WPE_, TRAIN_, IDT_, PERS_, ACT_>; }
+};
+
+// What a roll-out launcher does with a configuration (Backend::pick_rollout / pick_rollout_geo): launch the variant the flags name
+// -- pers: the queue form on as many workgroups as stay resident, else one workgroup per intersection -- or, launch = false,
+// answer 1 = no resident kernel: pve_step_many falls back to chunked, then per-tick launches
+struct RolloutPick {
+    bool launch;
+    bool wide;                   // k_rollout: the HOME build (WPE 5); k_rollout_geo: the knob-only 96-VGPR build
+    bool prof, act, train, idt, pers;
+};
+
+// Workgroups the current device holds at once of kernel variant Q, or -1 (err set): resident workgroups per CU x CUs, cached per
+// DEVICE (a process may hold handles on several GPUs, and they need not be the same part) and per queried kernel, hence per
+// capacity; filled by the first persistent launch on that device.
+template <typename Q> static long long resident_workgroups(std::string &err)
+{
+    static_assert(Q::exists && Q::PERS, "the grid is sized by a queue kernel the library holds");
+    constexpr int MAX_DEV = 64;
+    static std::mutex mu;
+    static int wgs[MAX_DEV] = {}, n_cu[MAX_DEV] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { err = "hipGetDevice failed"; return -1; }
+    std::lock_guard<std::mutex> lock(mu);
+    const bool cached = dev >= 0 && dev < MAX_DEV && wgs[dev] > 0;
+    int nb = cached ? wgs[dev] : 0, cus = cached ? n_cu[dev] : 0;
+    if (!cached) {
+        hipDeviceProp_t prop;
+        const hipError_t e = resident_blocks(&nb, Q::kernel(), Q::CAP);
+        if (e != hipSuccess || nb <= 0 || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
+            err = std::string("occupancy query of the persistent roll-out: ") + hipGetErrorString(e);
+            return -1;
+        }
+        cus = prop.multiProcessorCount;
+        if (dev >= 0 && dev < MAX_DEV) { wgs[dev] = nb; n_cu[dev] = cus; }
+    }
+    return (long long)nb * cus;
+}
 
 struct Backend {
     // the largest capacity pve_create accepts (pve_capi.inc): 256 slots for the 12-lane fast path
@@ -1101,66 +1149,89 @@ struct Backend {
         if (e != hipSuccess) { err = hip_err("kernel launch", e); return -1; }
         return 0;
     }
-    static int launch_tick(const Const &c, const Params &P, int cap, void *stream, std::string &err)
+    template <typename K, typename... A>
+    static int launch(K kernel, long long grid, int block, void *stream, std::string &err, const A &...args)
     {
-        hipStream_t s = (hipStream_t)stream;
-        if (cap == 64) hipLaunchKernelGGL(k_tick<64>, dim3(P.n_envs), dim3(64), 0, s, c, P);
-        else if (cap == 128) hipLaunchKernelGGL(k_tick<128>, dim3(P.n_envs), dim3(128), 0, s, c, P);
-        else if (cap == 256) hipLaunchKernelGGL(k_tick<256>, dim3(P.n_envs), dim3(256), 0, s, c, P);
-        else return bad_cap(cap, err);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(block), 0, (hipStream_t)stream, args...);
         return check_launch(err);
     }
-    static int launch_rollout(const Const &c, const Params &P_in, const RolloutArgs &R, int cap, void *stream, std::string &err)
+    // THE run-time capacity dispatch: f receives the capacity as std::integral_constant<int, CAP>.  MAX_CAP = 128: a kernel family
+    // without a 256-slot build (the 4- / 8-lane layouts)
+    template <int MAX_CAP = max_capacity, typename F> static int with_cap(int cap, std::string &err, F f)
     {
-        ActionNoise off;
-        memset(&off, 0, sizeof(off));
-        return launch_rollout_noisy(c, P_in, R, off, cap, stream, err);
+        if (cap == 64) return f(std::integral_constant<int, 64>{});
+        if (cap == 128) return f(std::integral_constant<int, 128>{});
+        if constexpr (MAX_CAP >= 256) if (cap == 256) return f(std::integral_constant<int, 256>{});
+        return bad_cap(cap, err);
     }
-    // launch_rollout + the exploration noise of the actor variants (nz.tick0 = the launch's first tick; read by the ACT variants only)
-    static int launch_rollout_noisy(const Const &c, const Params &P_in, const RolloutArgs &R, const ActionNoise &nz, int cap, void *stream,
-                                    std::string &err)
+    static int launch_tick(const Const &c, const Params &P, int cap, void *stream, std::string &err)
+    {
+        return with_cap(cap, err, [&](auto CAP) { return launch(k_tick<CAP()>, P.n_envs, CAP(), stream, err, c, P); });
+    }
+    // the kernel's view of the action source: the pool / table row of the launch's first tick, P.actions = that tick's actions of the
+    // pool, the exploration noise (a variant without the actor receives the RolloutArgs part)
+    static RolloutArgsNoisy rollout_source(const RolloutArgs &R, const ActionNoise &nz, int cap, Params &P)
+    {
+        RolloutArgsNoisy Rk;
+        (RolloutArgs &)Rk = R;
+        Rk.noise = nz;
+        if (R.source == 1 || R.source == 3) Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
+        P.actions = R.source == 1 ? R.pool + (size_t)Rk.pool_tick0 * (size_t)P.n_envs * (size_t)cap : nullptr;
+        return Rk;
+    }
+    // Launch variant V: one workgroup per intersection, or -- the persistent form (pve_rollout.persistent) -- as many workgroups as
+    // the chip holds at once of V::sized_by (the queue needs no more; fewer when the call has fewer items)
+    template <typename V, typename C>
+    static int launch_variant(const C &c, const Params &P, const RolloutArgsNoisy &Rk, void *stream, std::string &err)
+    {
+        if constexpr (!V::exists) {
+            err = "no such roll-out kernel variant";             // (a pick_rollout* that names a variant its family does not declare)
+            return -1;
+        } else {
+            long long grid = P.n_envs;
+            if constexpr (V::PERS) {
+                grid = resident_workgroups<typename V::sized_by>(err);
+                if (grid < 0) return -1;
+                const long long items = (long long)P.n_envs * (Rk.n_full + Rk.n_taper);
+                if (const char *g = PVE_KNOB("PVE_PERSISTENT_GRID")) { const long long v = atoll(g); if (v > 0) grid = v; }   // A/B knob
+                if (grid > items) grid = items;
+            }
+            return launch(V::kernel(), grid, V::CAP, stream, err, c, P, Rk);
+        }
+    }
+    // The axes of a configuration, and what rules a resident kernel out in both families: the A/B knobs, and for the closed loop
+    // the exact-float32 actor (per-tick launches run it) and a queue without R.actor_actions, through which an intersection's
+    // actions go from one item to the next
+    static RolloutPick rollout_axes(const Params &P, const RolloutArgs &R)
     {
         static const bool off = PVE_KNOB("PVE_NO_ROLLOUT_KERNEL") != nullptr;   // A/B knob: one launch per tick instead
         static const bool act_off = PVE_KNOB("PVE_NO_ROLLOUT_ACTOR") != nullptr;   // A/B knob: actor + tick launches instead
-        if (off || (R.source == 2 /* PVE_SRC_ACTOR */ && (act_off || R.exact_f32 || P_in.phase_cycles))) return 1;
-        hipStream_t s = (hipStream_t)stream;
-        Params P = P_in;
-        RolloutArgsNoisy Rk;                         // (a variant without the actor receives its RolloutArgs part)
-        (RolloutArgs &)Rk = R;
-        Rk.noise = nz;
-        if (R.source == 1) {
-            Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
-            P.actions = R.pool + (size_t)Rk.pool_tick0 * (size_t)P.n_envs * (size_t)cap;
-        } else P.actions = nullptr;
-        if (R.source == 3) Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
-        const bool train = P.out.obs_pre || P.out.state_pre;
-        const bool act = R.source == 2, idt = R.source == 3, pers = R.queue != nullptr;
-        long long grid = P.n_envs;
-        if (pers) {                                                           // persistent form (pve_rollout.persistent)
-            if (act && (act_off || R.exact_f32 || !R.actor_actions)) return 1;
-#ifdef PVE_QUEUE_TRACE
-            Rk.q_trace = P.phase_cycles;                                      // (per-item timestamps: make trace)
-#else
-            if (P.phase_cycles) return 1;       // pve_debug_phase_cycles armed: the chunked launches record the cycles (as the geo path does)
+        RolloutPick v = {};
+        v.act = R.source == 2 /* PVE_SRC_ACTOR */; v.idt = R.source == 3; v.pers = R.queue != nullptr;
+        v.train = P.out.obs_pre || P.out.state_pre;
+        v.launch = !off && !(v.act && (act_off || R.exact_f32 || (v.pers && !R.actor_actions)));
+        return v;
+    }
+    // Is there a resident / persistent k_rollout for this configuration, and which (variant = capacity x action source (pool / zero,
+    // actor, id-indexed table) x training outputs x launch form)
+    static RolloutPick pick_rollout(int cap, const Params &P, const RolloutArgs &R)
+    {
+        const RolloutPick none = {};
+        RolloutPick v = rollout_axes(P, R);
+        if (!v.launch) return none;
+        if (P.phase_cycles) {
+            // pve_debug_phase_cycles armed.  The phase-cycle diagnostics exist for the default kernel only: every other variant (table,
+            // actor, training outputs) answers "no resident kernel" and the caller falls back to per-tick launches, which record the
+            // cycles (256 slots: no diagnostics variant of the resident kernel either).  The queue form has none: the chunked launches
+            // record the cycles (as the geo path does) -- except in `make trace`, whose per-item timestamps go where the cycles would
+            if (v.act) return none;
+            if (!v.pers) {
+                if (v.train || v.idt || cap == 256) return none;
+                v.prof = true;
+            }
+#ifndef PVE_QUEUE_TRACE
+            else return none;
 #endif
-            // as many workgroups as the chip holds at once (the queue needs no more; fewer when the call has fewer items)
-            // (each capacity from its own kernel's occupancy: the 256-slot block admits half the 128-slot workgroups per CU)
-            grid = g_occ.resident(0, cap, [&](int *nb) {
-                if (cap == 64) return resident_blocks(nb, k_rollout<64, 4, false, false, false, false, true>, 64);
-                if (cap == 128) return resident_blocks(nb, k_rollout<128, 4, false, false, false, false, true>, 128);
-                return resident_blocks(nb, k_rollout<256, 4, false, false, false, false, true>, 256); }, err);
-            if (grid < 0) return -1;
-            const long long items = (long long)P.n_envs * (R.n_full + R.n_taper);
-            if (const char *g = PVE_KNOB("PVE_PERSISTENT_GRID")) { const long long v = atoll(g); if (v > 0) grid = v; }   // A/B knob
-            if (grid > items) grid = items;
-        } else if (P.phase_cycles) {
-            // the phase-cycle diagnostics exist for the default kernel only: every other variant (table, actor, training outputs)
-            // answers "no resident kernel" and the caller falls back to per-tick launches, which record the cycles
-            // (256 slots: no diagnostics variant of the resident kernel either)
-            if (train || idt || act || cap == 256) return 1;
-            if (cap == 64) hipLaunchKernelGGL((k_rollout<64, 4, true>), dim3(P.n_envs), dim3(64), 0, s, c, P, Rk);
-            else hipLaunchKernelGGL((k_rollout<128, 4, true>), dim3(P.n_envs), dim3(128), 0, s, c, P, Rk);
-            return check_launch(err);
         }
         // k_rollout<128, 5, ..>: the HOME build of the persistent kernel (128 slots; table, pool and zero sources) -- 96 registers
         // + the 15 264 B block with the carried per-slot fields in LDS homes = 10 workgroups per CU instead of 8, no scratch
@@ -1168,154 +1239,77 @@ struct Backend {
         // a plain launch of 4096 workgroups would run as 2560 + 1536.
         // (The training outputs through this block -- k_rollout<128, 5, .., TRAIN, .., PERS>: 94-96 registers -- were measured: 137-141
         //  against 129-131 us per tick; the trainer's roll-out keeps the register build.)
-        const bool home_ok = pers && !act && !train && cap == 128 && P.rows < (1 << 23);
-        bool home5 = PVE_HOME_DEFAULT != 0 && home_ok;
+        const bool home_ok = v.pers && !v.act && !v.train && cap == 128 && P.rows < (1 << 23);
+        v.wide = PVE_HOME_DEFAULT != 0 && home_ok;
 #ifdef PVE_AB_KNOBS
-        if (const char *k5 = getenv("PVE_ROLLOUT_WPE5")) home5 = atoi(k5) != 0 && home_ok;   // A/B knob
+        if (const char *k5 = getenv("PVE_ROLLOUT_WPE5")) v.wide = atoi(k5) != 0 && home_ok;   // A/B knob
 #endif
-        if (home5) {
-            long long g5 = g_occ.resident(3, cap, [&](int *nb) {
-                return resident_blocks(nb, k_rollout<128, 5, false, false, false, true, true>, 128); }, err);
-            if (g5 < 0) return -1;
-            const long long items = (long long)P.n_envs * (R.n_full + R.n_taper);
-            if (const char *g = PVE_KNOB("PVE_PERSISTENT_GRID")) { const long long v = atoll(g); if (v > 0) g5 = v; }   // A/B knob
-            if (g5 > items) g5 = items;
-            if (idt) hipLaunchKernelGGL((k_rollout<128, 5, false, false, false, true, true>), dim3((unsigned)g5), dim3(128), 0, s, c, P, Rk);
-            else hipLaunchKernelGGL((k_rollout<128, 5, false, false, false, false, true>), dim3((unsigned)g5), dim3(128), 0, s, c, P, Rk);
-            return check_launch(err);
-        }
-        // variant = capacity x action source (pool / zero, actor, id-indexed table) x training outputs x launch form
-        if (cap != 64 && cap != 128 && cap != 256) return bad_cap(cap, err);
-#define PVE_ROLLOUT(ACT_, TRAIN_, IDT_, PERS_)                                                                                           \
-        do {                                                                                                                             \
-            if (cap == 64) hipLaunchKernelGGL((k_rollout<64, 4, false, ACT_, TRAIN_, IDT_, PERS_>), dim3((unsigned)grid), dim3(64), 0, s, c, P, Rk);  \
-            else if (cap == 128) hipLaunchKernelGGL((k_rollout<128, 4, false, ACT_, TRAIN_, IDT_, PERS_>), dim3((unsigned)grid), dim3(128), 0, s, c, P, Rk);  \
-            else hipLaunchKernelGGL((k_rollout<256, 4, false, ACT_, TRAIN_, IDT_, PERS_>), dim3((unsigned)grid), dim3(256), 0, s, c, P, Rk);          \
-        } while (0)
-#define PVE_ROLLOUT_SRC(TRAIN_, PERS_)                                                                                                   \
-        do {                                                                                                                             \
-            if (act) PVE_ROLLOUT(true, TRAIN_, false, PERS_);                                                                            \
-            else if (idt) PVE_ROLLOUT(false, TRAIN_, true, PERS_);                                                                       \
-            else PVE_ROLLOUT(false, TRAIN_, false, PERS_);                                                                               \
-        } while (0)
-        if (train) { if (pers) PVE_ROLLOUT_SRC(true, true); else PVE_ROLLOUT_SRC(true, false); }
-        else { if (pers) PVE_ROLLOUT_SRC(false, true); else PVE_ROLLOUT_SRC(false, false); }
-#undef PVE_ROLLOUT_SRC
-#undef PVE_ROLLOUT
-        return check_launch(err);
+        return v;
     }
-    static int launch_rollout_geo(const GeoConst &g, const Params &P_in, const RolloutArgs &R, int cap, void *stream, std::string &err)
+    // pve_step_many's launch of a chunk or of the whole call, with the exploration noise of the actor variants (nz.tick0 = the
+    // launch's first tick; read by the ACT variants only) -> 0, 1 = no resident kernel for this configuration, -1 (err set)
+    static int launch_rollout_noisy(const Const &c, const Params &P_in, const RolloutArgs &R, const ActionNoise &nz, int cap, void *stream,
+                                    std::string &err)
     {
-        ActionNoise off;
-        memset(&off, 0, sizeof(off));
-        return launch_rollout_geo_noisy(g, P_in, R, off, cap, stream, err);
+        const RolloutPick v = pick_rollout(cap, P_in, R);
+        if (!v.launch) return 1;
+        Params P = P_in;
+        RolloutArgsNoisy Rk = rollout_source(R, nz, cap, P);
+#ifdef PVE_QUEUE_TRACE
+        if (v.pers) Rk.q_trace = P.phase_cycles;                              // (per-item timestamps: make trace)
+#endif
+        return with_cap(cap, err, [&](auto CAP) {
+            return with_flags([&](auto HOME, auto PROF, auto ACT, auto TRAIN, auto IDT, auto PERS) {
+                return launch_variant<Rollout12<CAP(), HOME() ? 5 : 4, PROF(), ACT(), TRAIN(), IDT(), PERS()>>(c, P, Rk, stream, err);
+            }, v.wide, v.prof, v.act, v.train, v.idt, v.pers);
+        });
+    }
+    static RolloutPick pick_rollout_geo(const GeoConst &g, int cap, const Params &P, const RolloutArgs &R)
+    {
+        const RolloutPick none = {};
+        RolloutPick v = rollout_axes(P, R);
+        // (no phase-cycle diagnostics in k_rollout_geo; the table source without the training outputs)
+        if (!v.launch || P.phase_cycles || (v.train && v.idt)) return none;
+        // (the closed loop with the training outputs is bound by the state writes: its queue form measured 130 against 128 us per
+        //  tick of chunked launches, so it stays on those.  Round 6: the 4-lane <TRAIN, PERS> variant is instantiated -- it
+        //  carries 32 spilled registers through the tick and is still 6 % faster than chunked launches: 95.3 vs 101.5 us)
+        if (v.pers && v.train && v.act) return none;
+#ifdef PVE_AB_KNOBS
+        static const bool w5 = getenv("PVE_ROLLOUT_GEO_WPE5") != nullptr;     // A/B knob: 96-VGPR build, 10 workgroups per CU (414 spills)
+        v.wide = w5 && cap == 128 && g.lane_num != 4 && !v.train && !v.act && !v.pers && !v.idt;
+#endif
+        return v;
     }
     static int launch_rollout_geo_noisy(const GeoConst &g, const Params &P_in, const RolloutArgs &R, const ActionNoise &nz, int cap,
                                         void *stream, std::string &err)
     {
-        static const bool off = PVE_KNOB("PVE_NO_ROLLOUT_KERNEL") != nullptr;   // A/B knob: one launch per tick instead
-        static const bool act_off = PVE_KNOB("PVE_NO_ROLLOUT_ACTOR") != nullptr;   // A/B knob: actor + tick launches instead
-        const bool train = P_in.out.obs_pre || P_in.out.state_pre;
-        const bool act = R.source == 2 /* PVE_SRC_ACTOR */;
-        if (off || P_in.phase_cycles || (train && R.source == 3)) return 1;
-        if (act && (act_off || R.exact_f32 || (R.queue && !R.actor_actions))) return 1;
-        if (cap != 64 && cap != 128) return bad_cap(cap, err);         // (the 4- / 8-lane layouts: 64 or 128 slots)
-        const bool fix4 = g.lane_num == 4;           // (the 4-lane layout's far-conflict path is a kernel of its own)
-        // (the closed loop with the training outputs is bound by the state writes: its queue form measured 130 against 128 us per
-        //  tick of chunked launches, so it stays on those.  Round 6: the 4-lane <TRAIN, PERS> variant is instantiated -- it
-        //  carries 32 spilled registers through the tick and is still 6 % faster than chunked launches: 95.3 vs 101.5 us)
-        if (R.queue && train && act) return 1;
-        hipStream_t s = (hipStream_t)stream;
+        const RolloutPick v = pick_rollout_geo(g, cap, P_in, R);
+        if (!v.launch) return 1;
         Params P = P_in;
-        RolloutArgsNoisy Rk;                         // (a variant without the actor receives its RolloutArgs part)
-        (RolloutArgs &)Rk = R;
-        Rk.noise = nz;
-        if (R.source == 1) {
-            Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
-            P.actions = R.pool + (size_t)Rk.pool_tick0 * (size_t)P.n_envs * (size_t)cap;
-        } else P.actions = nullptr;
-        if (R.source == 3) Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
-        dim3 grid(P.n_envs);
-        if (R.queue) {
-            // the persistent form: as many workgroups as the chip holds at once (the variants of one capacity share their register
-            // budget; the actor's parameters add 2 KB of LDS: a query of its own)
-            long long gq = g_occ.resident(act ? 2 : 1, cap, [&](int *nb) {
-                if (act) return (cap == 64) ? resident_blocks(nb, k_rollout_geo<64, true, 4, false, false, true, true>, 64)
-                                            : resident_blocks(nb, k_rollout_geo<128, true, 4, false, false, true, true>, 128);
-                return (cap == 64) ? resident_blocks(nb, k_rollout_geo<64, true, 4, false, false, true>, 64)
-                                   : resident_blocks(nb, k_rollout_geo<128, true, 4, false, false, true>, 128); }, err);
-            if (gq < 0) return -1;
-            const long long items = (long long)P.n_envs * (R.n_full + R.n_taper);
-            if (gq > items) gq = items;
-            grid = dim3((unsigned)gq);
-        }
-        // (variant = layout x capacity x {default, training outputs, id-indexed table, actor} x launch form)
-#define PVE_LAUNCH_GEO_V(CAP_, FIX_, TRAIN_, IDT_, PERS_, ACT_) \
-        hipLaunchKernelGGL((k_rollout_geo<CAP_, FIX_, 4, TRAIN_, IDT_, PERS_, ACT_>), grid, dim3(CAP_), 0, s, g, P, Rk)
-#define PVE_LAUNCH_GEO(CAP_, FIX_)                                                                                              \
-        do {                                                                                                                    \
-            if (R.queue) {                                                                                                       \
-                if (act) PVE_LAUNCH_GEO_V(CAP_, FIX_, false, false, true, true);                                            \
-                else if (train) PVE_LAUNCH_GEO_V(CAP_, FIX_, true, false, true, false);                                          \
-                else if (R.source == 3) PVE_LAUNCH_GEO_V(CAP_, FIX_, false, true, true, false);                                   \
-                else PVE_LAUNCH_GEO_V(CAP_, FIX_, false, false, true, false);                                                    \
-            }                                                                                                                    \
-            else if (act && train) PVE_LAUNCH_GEO_V(CAP_, FIX_, true, false, false, true);   /* (round 6: closed loop + training outputs) */ \
-            else if (act) PVE_LAUNCH_GEO_V(CAP_, FIX_, false, false, false, true);                                               \
-            else if (train) PVE_LAUNCH_GEO_V(CAP_, FIX_, true, false, false, false);                                             \
-            else if (R.source == 3) PVE_LAUNCH_GEO_V(CAP_, FIX_, false, true, false, false);                                     \
-            else PVE_LAUNCH_GEO_V(CAP_, FIX_, false, false, false, false);                                                       \
-        } while (0)
-        if (fix4) {
-            if (cap == 64) PVE_LAUNCH_GEO(64, true); else PVE_LAUNCH_GEO(128, true);
-        } else if (cap == 64) PVE_LAUNCH_GEO(64, false);
-        else {
-#ifdef PVE_AB_KNOBS
-            static const bool w5 = getenv("PVE_ROLLOUT_GEO_WPE5") != nullptr;     // A/B knob: 96-VGPR build, 10 workgroups per CU (414 spills)
-            if (w5 && !train && !act && !R.queue && R.source != 3) hipLaunchKernelGGL((k_rollout_geo<128, false, 5>), grid, dim3(128), 0, s, g, P, Rk);
-            else
-#endif
-            PVE_LAUNCH_GEO(128, false);
-        }
-#undef PVE_LAUNCH_GEO
-#undef PVE_LAUNCH_GEO_V
-        return check_launch(err);
+        const RolloutArgsNoisy Rk = rollout_source(R, nz, cap, P);
+        const bool fix4 = g.lane_num == 4;           // (the 4-lane layout's far-conflict path is a kernel of its own)
+        return with_cap<128>(cap, err, [&](auto CAP) {
+            return with_flags([&](auto FIX4, auto WPE5, auto TRAIN, auto IDT, auto PERS, auto ACT) {
+                return launch_variant<RolloutGeo<CAP(), FIX4(), WPE5() ? 5 : 4, TRAIN(), IDT(), PERS(), ACT()>>(g, P, Rk, stream, err);
+            }, fix4, v.wide, v.train, v.idt, v.pers, v.act);
+        });
     }
     static int launch_tick_geo(const GeoConst &g, const Params &P, int cap, void *stream, std::string &err)
     {
-        hipStream_t s = (hipStream_t)stream;
-        if (cap != 64 && cap != 128) return bad_cap(cap, err);         // (the 4- / 8-lane layouts: 64 or 128 slots)
-        // (the 4-lane layout's far-conflict path is a kernel of its own: FIX4)
-        if (g.lane_num == 4) {
-            if (P.phase_cycles) {                                    // diagnostics build (pve_debug_phase_cycles)
-                if (cap == 64) hipLaunchKernelGGL((k_tick_geo<64, true, true>), dim3(P.n_envs), dim3(64), 0, s, g, P);
-                else hipLaunchKernelGGL((k_tick_geo<128, true, true>), dim3(P.n_envs), dim3(128), 0, s, g, P);
-            } else if (cap == 64) hipLaunchKernelGGL((k_tick_geo<64, false, true>), dim3(P.n_envs), dim3(64), 0, s, g, P);
-            else hipLaunchKernelGGL((k_tick_geo<128, false, true>), dim3(P.n_envs), dim3(128), 0, s, g, P);
-        } else if (P.phase_cycles) {
-            if (cap == 64) hipLaunchKernelGGL((k_tick_geo<64, true>), dim3(P.n_envs), dim3(64), 0, s, g, P);
-            else hipLaunchKernelGGL((k_tick_geo<128, true>), dim3(P.n_envs), dim3(128), 0, s, g, P);
-        } else if (cap == 64) hipLaunchKernelGGL((k_tick_geo<64, false>), dim3(P.n_envs), dim3(64), 0, s, g, P);
-        else hipLaunchKernelGGL((k_tick_geo<128, false>), dim3(P.n_envs), dim3(128), 0, s, g, P);
-        return check_launch(err);
+        // (PROF: the diagnostics build, pve_debug_phase_cycles; FIX4: the 4-lane layout's far-conflict path is a kernel of its own)
+        return with_cap<128>(cap, err, [&](auto CAP) {
+            return with_flags([&](auto PROF, auto FIX4) {
+                return launch(k_tick_geo<CAP(), PROF(), FIX4()>, P.n_envs, CAP(), stream, err, g, P);
+            }, P.phase_cycles != nullptr, g.lane_num == 4);
+        });
     }
     static int launch_reset_geo(const GeoConst &g, const Params &P, int cap, void *stream, std::string &err)
     {
-        hipStream_t s = (hipStream_t)stream;
-        const int blocks = (P.n_envs + 63) / 64;
-        if (cap == 64) hipLaunchKernelGGL(k_reset_geo<64>, dim3(blocks), dim3(64), 0, s, g, P, 200000);
-        else if (cap == 128) hipLaunchKernelGGL(k_reset_geo<128>, dim3(blocks), dim3(64), 0, s, g, P, 200000);
-        else return bad_cap(cap, err);
-        return check_launch(err);
+        return with_cap<128>(cap, err, [&](auto CAP) { return launch(k_reset_geo<CAP()>, (P.n_envs + 63) / 64, 64, stream, err, g, P, 200000); });
     }
     static int launch_compact(const Params &P, int cap, void *stream, std::string &err)
     {
-        hipStream_t s = (hipStream_t)stream;
-        if (cap == 64) hipLaunchKernelGGL(k_compact<64>, dim3(P.n_envs), dim3(64), 0, s, P);
-        else if (cap == 128) hipLaunchKernelGGL(k_compact<128>, dim3(P.n_envs), dim3(128), 0, s, P);
-        else if (cap == 256) hipLaunchKernelGGL(k_compact<256>, dim3(P.n_envs), dim3(256), 0, s, P);
-        else return bad_cap(cap, err);
-        return check_launch(err);
+        return with_cap(cap, err, [&](auto CAP) { return launch(k_compact<CAP()>, P.n_envs, CAP(), stream, err, P); });
     }
     static int pack_actor(const float *W, float *flat, unsigned char *packed, void *stream, std::string &err)
     {
@@ -1324,24 +1318,6 @@ struct Backend {
         if (e != hipSuccess) { err = hip_err("hipMemcpyAsync", e); return -1; }
         hipLaunchKernelGGL(k_actor_pack, dim3(1), dim3(256), 0, s, W, packed);
         return check_launch(err);
-    }
-    template <typename OBS_T>
-    static void launch_actor_t(const float *W, const unsigned char *packed, const OBS_T *obs, const int32_t *meta, double *actions,
-                               int n_envs, int cap, bool exact_f32, const int32_t *ids, const ActionNoise &nz, hipStream_t s)
-    {
-        // persistent workgroups of 4 waves (the parameters are staged in LDS once per workgroup): 4 per CU, one wave
-        // per intersection at a time (a wave's second intersection, n_envs > 4096: tests/test_gpu_actor_streaming.py)
-        static const int wgs = [] { const char *g = PVE_KNOB("PVE_ACTOR_GRID"); const int v = g ? atoi(g) : 0; return v > 0 ? v : 1024; }();
-        const int grid = (n_envs + 3) / 4 < wgs ? (n_envs + 3) / 4 : wgs;
-        if (exact_f32) {
-            if (cap == 64) hipLaunchKernelGGL((k_actor_t<64, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs, ids, nz);
-            else if (cap == 128) hipLaunchKernelGGL((k_actor_t<128, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs, ids, nz);
-            else hipLaunchKernelGGL((k_actor_t<256, OBS_T>), dim3(grid), dim3(256), 0, s, W, obs, meta, actions, n_envs, ids, nz);
-        } else {
-            if (cap == 64) hipLaunchKernelGGL((k_actor_h<64, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs, ids, nz);
-            else if (cap == 128) hipLaunchKernelGGL((k_actor_h<128, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs, ids, nz);
-            else hipLaunchKernelGGL((k_actor_h<256, OBS_T>), dim3(grid), dim3(256), 0, s, packed, obs, meta, actions, n_envs, ids, nz);
-        }
     }
     static int launch_actor(const float *W, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
                             double *actions, int n_envs, int cap, void *stream, std::string &err)
@@ -1356,22 +1332,24 @@ struct Backend {
                                   const int32_t *ids, const ActionNoise &nz, double *actions, int n_envs, int cap, void *stream,
                                   std::string &err)
     {
-        hipStream_t s = (hipStream_t)stream;
-        if (cap != 64 && cap != 128 && cap != 256) return bad_cap(cap, err);
-        if (mode & 1) launch_actor_t<float>(W, packed, (const float *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, ids, nz, s);
-        else launch_actor_t<double>(W, packed, (const double *)obs, meta, actions, n_envs, cap, (mode & 2) != 0, ids, nz, s);
-        return check_launch(err);
+        // persistent workgroups of 4 waves (the parameters are staged in LDS once per workgroup): 4 per CU, one wave
+        // per intersection at a time (a wave's second intersection, n_envs > 4096: tests/test_gpu_actor_streaming.py)
+        static const int wgs = [] { const char *g = PVE_KNOB("PVE_ACTOR_GRID"); const int v = g ? atoi(g) : 0; return v > 0 ? v : 1024; }();
+        const int grid = (n_envs + 3) / 4 < wgs ? (n_envs + 3) / 4 : wgs;
+        return with_cap(cap, err, [&](auto CAP) {
+            return with_flags([&](auto OBS_F32, auto EXACT_F32) {
+                typedef std::conditional_t<OBS_F32(), float, double> OBS_T;
+                if constexpr (EXACT_F32()) return launch(k_actor_t<CAP(), OBS_T>, grid, 256, stream, err, W, (const OBS_T *)obs, meta, actions, n_envs, ids, nz);
+                else return launch(k_actor_h<CAP(), OBS_T>, grid, 256, stream, err, packed, (const OBS_T *)obs, meta, actions, n_envs, ids, nz);
+            }, (mode & 1) != 0, (mode & 2) != 0);
+        });
     }
     // pve_set_target_networks: the target actor through the actor's own packing kernel, the critic through k_critic_pack
     static int pack_target_networks(const float *actor_w, float *actor_flat, unsigned char *actor_packed, const float *critic_w,
                                     float *critic_flat, unsigned char *critic_packed, void *stream, std::string &err)
     {
         hipStream_t s = (hipStream_t)stream;
-        if (actor_w) {
-            hipError_t e = hipMemcpyAsync(actor_flat, actor_w, sizeof(float) * AW_TOTAL, hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) { err = hip_err("hipMemcpyAsync", e); return -1; }
-            hipLaunchKernelGGL(k_actor_pack, dim3(1), dim3(256), 0, s, actor_w, actor_packed);
-        }
+        if (actor_w && pack_actor(actor_w, actor_flat, actor_packed, stream, err) != 0) return -1;
         if (critic_w) {
             hipError_t e = hipMemcpyAsync(critic_flat, critic_w, sizeof(float) * CW_TOTAL, hipMemcpyDeviceToDevice, s);
             if (e != hipSuccess) { err = hip_err("hipMemcpyAsync", e); return -1; }
@@ -1425,22 +1403,11 @@ struct Backend {
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)
     {
-        hipStream_t s = (hipStream_t)stream;
-        if (cap == 64) hipLaunchKernelGGL(k_probe<64>, dim3(P.n_envs), dim3(64), 0, s, P, sink);
-        else if (cap == 128) hipLaunchKernelGGL(k_probe<128>, dim3(P.n_envs), dim3(128), 0, s, P, sink);
-        else if (cap == 256) hipLaunchKernelGGL(k_probe<256>, dim3(P.n_envs), dim3(256), 0, s, P, sink);
-        else return bad_cap(cap, err);
-        return check_launch(err);
+        return with_cap(cap, err, [&](auto CAP) { return launch(k_probe<CAP()>, P.n_envs, CAP(), stream, err, P, sink); });
     }
     static int launch_reset(const Const &c, const Params &P, int cap, void *stream, std::string &err)
     {
-        hipStream_t s = (hipStream_t)stream;
-        const int blocks = (P.n_envs + 63) / 64;
-        if (cap == 64) hipLaunchKernelGGL(k_reset<64>, dim3(blocks), dim3(64), 0, s, c, P, 200000);
-        else if (cap == 128) hipLaunchKernelGGL(k_reset<128>, dim3(blocks), dim3(128 / 2), 0, s, c, P, 200000);
-        else if (cap == 256) hipLaunchKernelGGL(k_reset<256>, dim3(blocks), dim3(64), 0, s, c, P, 200000);
-        else return bad_cap(cap, err);
-        return check_launch(err);
+        return with_cap(cap, err, [&](auto CAP) { return launch(k_reset<CAP()>, (P.n_envs + 63) / 64, 64, stream, err, c, P, 200000); });
     }
 };
 
