@@ -337,6 +337,58 @@ typedef struct pve_nstep {
 int pve_nstep_scan(pve_handle h, const pve_nstep *ns);
 int pve_nstep_gather(pve_handle h, const pve_nstep *ns);
 
+/* REPLAY MEMORY on the device: the uniform store and draw between pve_nstep_gather and pve_critic_forward (reference
+ * replay_buffer.py:45-53 `add` and :20-23 `getBatch` with rand_s = True, i.e. `ReplayBuffer(500000, batch_size, learn_start, 50000,
+ * rand_s=True)`; main.py:263 `agent1_memory_seq.add(...)`, main.py:50-77 `agent_memory.getBatch(batch_size)` and the split of the batch
+ * into obs_batch, the 7 actions and target).  Additive within ABI 9: three new symbols and one new struct, nothing existing changes,
+ * PVE_ABI_VERSION stays 9; a binding detects an older library by the missing symbols.
+ *
+ * RING.  `store` holds `capacity` records of PVE_NSTEP_RECORD = 36 float32 in caller-owned DEVICE memory, `state` is a DEVICE block
+ * of PVE_REPLAY_STATE_WORDS int64: state[0] = written (adds ever made = the reference's count()), state[1] = draws (minibatches
+ * ever drawn), state[2] = status (live records seen by the latest pve_replay_sample), state[3] reserved.  Record number w (0-based
+ * over all adds) lives in slot w mod capacity; the live records are the last L = min(written, capacity), age index a in [0, L) names
+ * record written - L + a (0 = the oldest, the left end of the reference's deque).  The reference's deque holds buffer_size - 1
+ * entries (num_experiences is incremented before the `<` test, replay_buffer.py:47-49): capacity = 499999 is its 500000.
+ * The handle only supplies the device and the stream; one memory belongs to one handle's stream at a time.
+ *
+ * pve_replay_reset (the reference builds a new ReplayBuffer, main.py:212) zeroes the state block; the store needs no clearing.
+ * pve_replay_append (replay_buffer.py:45-53) appends the first n = min(*total_dev, n_max) records of `records` in order; total_dev
+ * is a DEVICE int64 (pve_nstep.total, so there is no host synchronisation; negative counts as 0) or NULL for n = n_max.  Of a
+ * chunk with n > capacity only the last `capacity` records are written (the others would be overwritten within the same call),
+ * `written` grows by n.  records must not overlap the store.
+ * pve_replay_sample (replay_buffer.py:20-23, main.py:50-77) draws n_batches minibatches of `batch` distinct live records each --
+ * uniform, without replacement within a minibatch -- and writes them split the way pve_critic_forward(rows, act7) takes them:
+ *   rows float32 [n_batches][batch][28], act7 float32 [n_batches][batch][7], target float32 [n_batches][batch],
+ *   seq int64 [n_batches][batch] = the record numbers w.
+ * With fewer than `batch` live records (the reference raises ValueError) it writes seq = -1 and zeros and leaves `draws` alone;
+ * otherwise draws grows by n_batches.  Either way state[2] = L, which a caller may read to tell the two apart.
+ * THE DRAW (csrc/pve_replay.h, restated in pve_mcc_amd/replay.py; the reference's Mersenne-Twister draw is not reproduced):
+ * minibatch number d = draws, draws + 1, .. takes the age indices perm(seed, d, L)(j), j = 0 .. batch - 1, where perm(seed, d, N) is
+ * a bijection of [0, N) and a pure function of its arguments (not of the launch geometry, the batch size or n_batches):
+ *   b = bit length of N - 1, at least 2, rounded up to even, h = b / 2; an 8-round Feistel network over (L, R) = the high / low h bits,
+ *   (L, R) <- (R, L ^ F_r(R)), r = 0 .. 7, with F_r(R) = output word 0, masked to h bits, of Philox4x32-10 with
+ *   counter = (R, r, d low word, d high word) and key = (seed low word ^ 0x5245504C, seed high word ^ 0x41594D45)
+ *   (the tag keeps these inputs apart from pve_set_action_noise's, whose key is the bare seed); cycle walk: x = j, then
+ *   x <- Feistel(x) until x < N.
+ * block_threads: 0 = default; diagnostics: threads per workgroup of both kernels (a multiple of 64, <= 1024; same results).
+ * Errors (PVE_ERR_INVALID): null pointers, capacity outside 1 .. 2^31 - 1, batch < 1, batch > capacity, n_batches < 1,
+ * batch * n_batches > 2^31 - 1, n_max < 0, store / records / rows / act7 not 16-byte aligned (state / total_dev / seq: 8,
+ * target: 4), a bad block_threads, a backend without the kernels.  All three calls are asynchronous on the handle's stream and
+ * need no pve_reset. */
+#define PVE_REPLAY_STATE_WORDS 4
+typedef struct pve_replay {
+    int64_t capacity;             /* records */
+    float *store;                 /* DEVICE [capacity][36] */
+    int64_t *state;               /* DEVICE [PVE_REPLAY_STATE_WORDS] */
+    uint64_t seed;                /* of the draw */
+    int32_t block_threads;
+} pve_replay;
+int pve_replay_reset(pve_handle h, const pve_replay *rp);
+int pve_replay_append(pve_handle h, const pve_replay *rp, const float *records /* [n_max][36] */,
+                      const int64_t *total_dev /* DEVICE, or NULL */, int64_t n_max);
+int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t n_batches, float *rows, float *act7,
+                      float *target, int64_t *seq);
+
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly
  * pve_step_all() with

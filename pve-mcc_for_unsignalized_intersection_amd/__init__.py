@@ -3,5 +3,6 @@ Mingtzge/PVE-MCC_for_unsignalized_intersection): Python host code over hand-writ
 behind a C ABI (include/pve_env.h -> libpveenv.so)."""
 from ._capi import PveError, load_library  # noqa: F401
 from .batched import BatchedIntersections, PipelinedIntersections  # noqa: F401
+from .replay import ReplayMemory, ReplayModel  # noqa: F401
 
-__all__ = ["BatchedIntersections", "PipelinedIntersections", "PveError", "load_library"]
+__all__ = ["BatchedIntersections", "PipelinedIntersections", "PveError", "ReplayMemory", "ReplayModel", "load_library"]

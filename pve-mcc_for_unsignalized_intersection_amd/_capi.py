@@ -24,6 +24,7 @@ PVE_ENV_OUT_N = 8
 PVE_ACTOR_N_WEIGHTS = 6393
 PVE_CRITIC_N_WEIGHTS = 6841
 NSTEP_TAIL, NSTEP_MAX_WINDOW, NSTEP_RECORD = 0x1, 16, 36
+REPLAY_STATE_WORDS = 4
 ABI_VERSION = 9
 SRC_ZERO, SRC_POOL, SRC_ACTOR, SRC_TABLE = 0, 1, 2, 3
 
@@ -70,6 +71,11 @@ class PveNstep(C.Structure):
                 ("records", C.c_void_p), ("index", C.c_void_p), ("block_threads", C.c_int32)]
 
 
+class PveReplay(C.Structure):
+    _fields_ = [("capacity", C.c_int64), ("store", C.c_void_p), ("state", C.c_void_p), ("seed", C.c_uint64),
+                ("block_threads", C.c_int32)]
+
+
 class PveVehicle(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("p", "v", "a", "jerk", "jerk_sum", "vir_dis", "closer_p")] + \
                [(n, C.c_int32) for n in ("lane", "j", "id", "vnum", "seq_in_lane", "control", "finish", "done",
@@ -91,7 +97,8 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_state_field", "pve_synchronize", "pve_debug_phase_cycles", "pve_actor_forward",
            "pve_step_all_actor", "pve_debug_traffic_probe", "pve_set_intentions", "pve_step_many", "pve_set_actor",
            "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise",
-           "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather")
+           "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather",
+           "pve_replay_reset", "pve_replay_append", "pve_replay_sample")
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -129,6 +136,9 @@ def _declare(L):
     L.pve_bootstrap_q.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
     L.pve_nstep_scan.argtypes = [vp, C.POINTER(PveNstep)]
     L.pve_nstep_gather.argtypes = [vp, C.POINTER(PveNstep)]
+    L.pve_replay_reset.argtypes = [vp, C.POINTER(PveReplay)]
+    L.pve_replay_append.argtypes = [vp, C.POINTER(PveReplay), vp, vp, C.c_int64]
+    L.pve_replay_sample.argtypes = [vp, C.POINTER(PveReplay), C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
     for name in EXPORTS:

@@ -720,7 +720,8 @@ class PipelinedIntersections:
     Ordering is per sub-batch: `step()` enqueues on `streams[k]`; produce the actions of sub-batch k on that stream (or
     call `wait_stream()` after producing them elsewhere) and consume its outputs on that stream or after
     `synchronize()`.  This is the usual two-batch pipelining of an RL loop: policy inference for one half while the
-    environment steps the other.
+    environment steps the other.  A replay memory (replay.ReplayMemory) binds to ONE sub-batch's handle and stream
+    (`ReplayMemory(pipe.subs[k], ...)`); it is not fanned out over the sub-batches.
     """
 
     def __init__(self, n_envs, capacity, arrivals, n_sub=2, device=None, outputs=DEFAULT_OUTPUTS, intentions=None,

@@ -43,6 +43,11 @@
 //     static int   launch_nstep_scan(const pve::NstepArgs &, int block_threads, void *stream, std::string &err);
 //     static int   launch_nstep_gather(const pve::NstepArgs &, void *stream, std::string &err);
 //                                                // optional, both or none: pve_nstep_scan / pve_nstep_gather (csrc/pve_nstep.h)
+//     static int   launch_replay_append(const pve::ReplayArgs &, const float *records, const long long *total_dev, long long n_max,
+//                                       int block_threads, void *stream, std::string &err);
+//     static int   launch_replay_sample(const pve::ReplayArgs &, long long batch, long long n_batches, float *rows, float *act7,
+//                                       float *target, long long *seq, int block_threads, void *stream, std::string &err);
+//                                                // optional, both or none: pve_replay_reset / _append / _sample (csrc/pve_replay.h)
 //   };
 //
 // pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
@@ -231,6 +236,24 @@ template <class B> struct backend_nstep<B, decltype((void)&B::launch_nstep_gathe
     static constexpr bool value = true;
     static int scan(const NstepArgs &A, int block, void *stream, std::string &err) { return B::launch_nstep_scan(A, block, stream, err); }
     static int gather(const NstepArgs &A, void *stream, std::string &err) { return B::launch_nstep_gather(A, stream, err); }
+};
+// The replay memory (pve_replay_reset / pve_replay_append / pve_replay_sample) needs the kernels of pve_replay.h:
+// Backend::launch_replay_append / launch_replay_sample (detected by the second).  A backend without them exports the entry points
+// all the same; they validate their arguments and then refuse with PVE_ERR_INVALID.
+template <class B, class = void> struct backend_replay {
+    static constexpr bool value = false;
+    static int append(const ReplayArgs &, const float *, const long long *, long long, int, void *, std::string &) { return -1; }
+    static int sample(const ReplayArgs &, long long, long long, float *, float *, float *, long long *, int, void *, std::string &) { return -1; }
+};
+template <class B> struct backend_replay<B, decltype((void)&B::launch_replay_sample)> {
+    static constexpr bool value = true;
+    static int append(const ReplayArgs &A, const float *records, const long long *total_dev, long long n_max, int block, void *stream,
+                      std::string &err) { return B::launch_replay_append(A, records, total_dev, n_max, block, stream, err); }
+    static int sample(const ReplayArgs &A, long long batch, long long n_batches, float *rows, float *act7, float *target, long long *seq,
+                      int block, void *stream, std::string &err)
+    {
+        return B::launch_replay_sample(A, batch, n_batches, rows, act7, target, seq, block, stream, err);
+    }
 };
 extern "C" {
 
@@ -587,6 +610,77 @@ int pve_nstep_gather(pve_handle h, const pve_nstep *ns)
     DevScope dev_scope(h->device);
     std::string err;
     if (backend_nstep<Backend>::gather(A, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_nstep_gather: " + err);
+    return PVE_OK;
+}
+
+// pve_replay -> ReplayArgs, with the checks the three entry points share
+static int replay_args(pve_handle h, const pve_replay *rp, const char *who, ReplayArgs &A)
+{
+    const std::string w(who);
+    if (!h || !rp) return fail(PVE_ERR_INVALID, w + ": null argument");
+    if (!rp->store || !rp->state) return fail(PVE_ERR_INVALID, w + ": null store or state");
+    if (rp->capacity < 1 || rp->capacity > 0x7fffffffLL) return fail(PVE_ERR_INVALID, w + ": capacity must be 1 .. 2^31 - 1");
+    if (rp->block_threads < 0 || rp->block_threads > 1024 || rp->block_threads % 64)
+        return fail(PVE_ERR_INVALID, w + ": block_threads must be 0 or a multiple of 64 up to 1024");
+    if (((uintptr_t)rp->store & 15) || ((uintptr_t)rp->state & 7))
+        return fail(PVE_ERR_INVALID, w + ": store must be 16-byte aligned, state 8-byte aligned");
+    A.capacity = rp->capacity; A.store = rp->store; A.state = (long long *)rp->state; A.seed = rp->seed;
+    return PVE_OK;
+}
+
+static int no_replay_kernels(const char *who)
+{
+    return fail(PVE_ERR_INVALID, std::string(who) + ": this backend has no replay kernels");
+}
+
+int pve_replay_reset(pve_handle h, const pve_replay *rp)
+{
+    ReplayArgs A;
+    const int rc = replay_args(h, rp, "pve_replay_reset", A);
+    if (rc != PVE_OK) return rc;
+    if (!backend_replay<Backend>::value) return no_replay_kernels("pve_replay_reset");
+    DevScope dev_scope(h->device);
+    if (Backend::memset0(A.state, sizeof(long long) * REPLAY_STATE_WORDS, h->stream) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_replay_reset: device memset failed");
+    return PVE_OK;
+}
+
+int pve_replay_append(pve_handle h, const pve_replay *rp, const float *records, const int64_t *total_dev, int64_t n_max)
+{
+    ReplayArgs A;
+    const int rc = replay_args(h, rp, "pve_replay_append", A);
+    if (rc != PVE_OK) return rc;
+    if (n_max < 0) return fail(PVE_ERR_INVALID, "pve_replay_append: n_max must be >= 0");
+    if (n_max > 0 && !records) return fail(PVE_ERR_INVALID, "pve_replay_append: null records");
+    if (((uintptr_t)records & 15) || ((uintptr_t)total_dev & 7))
+        return fail(PVE_ERR_INVALID, "pve_replay_append: records must be 16-byte aligned, total_dev 8-byte aligned");
+    if (!backend_replay<Backend>::value) return no_replay_kernels("pve_replay_append");
+    if (n_max == 0) return PVE_OK;
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_replay<Backend>::append(A, records, (const long long *)total_dev, (long long)n_max, rp->block_threads, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_replay_append: " + err);
+    return PVE_OK;
+}
+
+int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t n_batches, float *rows, float *act7, float *target,
+                      int64_t *seq)
+{
+    ReplayArgs A;
+    const int rc = replay_args(h, rp, "pve_replay_sample", A);
+    if (rc != PVE_OK) return rc;
+    if (batch < 1 || batch > rp->capacity) return fail(PVE_ERR_INVALID, "pve_replay_sample: batch must be 1 .. capacity");
+    if (n_batches < 1 || n_batches > 0x7fffffffLL / batch)
+        return fail(PVE_ERR_INVALID, "pve_replay_sample: n_batches must be >= 1 and batch * n_batches <= 2^31 - 1");
+    if (!rows || !act7 || !target || !seq) return fail(PVE_ERR_INVALID, "pve_replay_sample: null output");
+    if (((uintptr_t)rows & 15) || ((uintptr_t)act7 & 15) || ((uintptr_t)target & 3) || ((uintptr_t)seq & 7))
+        return fail(PVE_ERR_INVALID, "pve_replay_sample: rows and act7 must be 16-byte aligned, seq 8-byte, target 4-byte aligned");
+    if (!backend_replay<Backend>::value) return no_replay_kernels("pve_replay_sample");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_replay<Backend>::sample(A, (long long)batch, (long long)n_batches, rows, act7, target, (long long *)seq, rp->block_threads,
+                                        h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_replay_sample: " + err);
     return PVE_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "pve_actor.h"
 #include "pve_critic.h"
 #include "pve_nstep.h"
+#include "pve_replay.h"
 
 using namespace pve;
 
@@ -1399,6 +1400,31 @@ struct Backend {
         const dim3 grid((unsigned)((n_slots + 255) / 256));
         if (A.obs_f32) hipLaunchKernelGGL(k_nstep_gather<float>, grid, dim3(256), 0, s, A, n_slots);
         else hipLaunchKernelGGL(k_nstep_gather<double>, grid, dim3(256), 0, s, A, n_slots);
+        return check_launch(err);
+    }
+    // pve_replay_append: the copy (grid-stride over the 16-byte pieces of at most min(n_max, capacity) records), then the state
+    // update in a launch of its own behind it -- no workgroup of the copy can read the new `written`
+    static int launch_replay_append(const ReplayArgs &A, const float *records, const long long *total_dev, long long n_max,
+                                    int block_threads, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int block = block_threads > 0 ? block_threads : 256;
+        const long long pieces = (n_max < A.capacity ? n_max : A.capacity) * REPLAY_PIECES, want = (pieces + block - 1) / block;
+        const unsigned grid = (unsigned)(want < 16384 ? want : 16384);
+        hipLaunchKernelGGL(k_replay_append, dim3(grid), dim3(block), 0, s, A, records, total_dev, n_max);
+        hipLaunchKernelGGL(k_replay_append_commit, dim3(1), dim3(64), 0, s, A, total_dev, n_max);
+        return check_launch(err);
+    }
+    // pve_replay_sample: one thread per drawn record, then `draws` and the status word in a launch of their own
+    static int launch_replay_sample(const ReplayArgs &A, long long batch, long long n_batches, float *rows, float *act7, float *target,
+                                    long long *seq, int block_threads, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int block = block_threads > 0 ? block_threads : 256;
+        const long long n_total = batch * n_batches;
+        hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)((n_total + block - 1) / block)), dim3(block), replay_sample_lds(block), s, A, batch,
+                           n_total, rows, act7, target, seq);
+        hipLaunchKernelGGL(k_replay_sample_commit, dim3(1), dim3(64), 0, s, A, batch, n_batches);
         return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)

@@ -10,8 +10,14 @@
 #include "../../include/pve_env.h"
 #include "pve_types.h"
 #include "pve_nstep.h"
+#include "pve_replay.h"
 
 namespace pve {
+
+// the replay memory stores the n-step pass's records, and its state block is the public one
+static_assert(REPLAY_REC == NSTEP_REC && REPLAY_REC == PVE_NSTEP_RECORD, "pve_replay.h and pve_nstep.h / pve_env.h disagree on the record");
+static_assert(REPLAY_STATE_WORDS == PVE_REPLAY_STATE_WORDS, "pve_replay.h and pve_env.h disagree on the state block");
+static_assert(sizeof(long long) == sizeof(int64_t), "the state block is int64");
 
 // Geometry and limits exactly as the reference constructor derives them
 // (ref traffic_interaction_scene.py:21-45, :148-152, :153-166, :182-186; libm = CPython's math).
