@@ -1235,7 +1235,7 @@ struct Backend {
 #endif
         }
         // k_rollout<128, 5, ..>: the HOME build of the persistent kernel (128 slots; table, pool and zero sources) -- 96 registers
-        // + the 15 264 B block with the carried per-slot fields in LDS homes = 10 workgroups per CU instead of 8, no scratch
+        // + the 15 280 B block with the carried per-slot fields in LDS homes = 10 workgroups per CU instead of 8, no scratch
         // (pve_tick_core.h: Homes).  Its packed seq_in_lane | id_info[1] word holds arrival cursors < 2^23.  Only the queue form:
         // a plain launch of 4096 workgroups would run as 2560 + 1536.
         // (The training outputs through this block -- k_rollout<128, 5, .., TRAIN, .., PERS>: 94-96 registers -- were measured: 137-141

@@ -41,6 +41,13 @@ namespace pve {
 
 typedef unsigned long long u64;
 
+// PVE_EMU_DIAG (tests/emu_diag only: the CPU emulator built with counters of what the streams make RANK do): how many lists of
+// each length the 128-slot blocks have laid out (lengths >= 63 share the last cell) and how many RANK fix-ups ran -- [0] by the
+// second entry of a pair whose partner shares its distance, [1] all others
+#if !PVE_DEVICE_CODE && defined(PVE_EMU_DIAG)
+inline int emu_diag_list_len[64], emu_diag_ties[2];
+#endif
+
 // ------------------------------------------------------------------ wave / block primitives
 template <int NW> PVE_HD void vote(u64 *m, int t, bool f)
 {
@@ -383,7 +390,7 @@ template <int CAP> constexpr int SLOT_NONE = CAP <= 128 ? 255 : 0xFFFF;
 // virdis[], p / v / a in p[] / v[] / a[] (S1 reads them there, and the next action in act_next[], instead of RELOAD handing
 // them over in registers).  When vehicles move, a thread takes its values at the very end of FIN (the registers of the
 // observation row are free again) and puts them at the new slot behind barrier A.  The entry pool shrinks to 304 entries to pay
-// for the homes AND to bring the block down to 15 264 B = 12 LDS granules of 1 280 B: ten workgroups per CU are resident only
+// for the homes AND to bring the block down to 15 280 B <= 12 LDS granules of 1 280 B: ten workgroups per CU are resident only
 // at <= 15 360 B (tools/occupancy_probe.hip; the runtime's occupancy query says ten up to 16 384 B, the hardware starts nine).
 // BUILD .. WALK run in passes over groups of lists when a tick needs more entries than the pool holds.
 template <int CAP> struct Homes {
@@ -470,15 +477,21 @@ struct Shared : std::conditional<HOME_, Homes<CAP>, HomesOff<CAP>>::type {
         // entries of list d with a finite distance (own lane + the chosen conflict entries, ref :259-270): RANK sorts only
         // those, WALK never sees an unchosen entry (LISTS .. WALK; the masks below are born in FX)
         int nfin[NL];
+        // CAP >= 128: RANK works on PAIRS of consecutive entries of one list (the last entry of an odd list is a pair of its
+        // own).  lpo()[d] = loff[d] | first pair of list d << 16, so that BUILD and RANK get both offsets with one read
+        // (LISTS .. RANK); the 13 words lie behind nfin, over masks that are born in FX
+        int nfin_lpo[DIRECT ? NL : 2 * NL + 1];
         struct {
             u64 m_del[NW], m_fin[NW], m_ctlnow[NW], m_coll[NW];
             union { u64 m_lead[NW]; u64 m_keep[NW]; };   // tick kernel | compaction kernel
             u64 m_spawn[NW];
         };
     };
+    PVE_HD int *lpo() { return nfin_lpo + (DIRECT ? 0 : NL); }
+    PVE_HD const int *lpo() const { return nfin_lpo + (DIRECT ? 0 : NL); }
     uint8_t s_slot[DIRECT ? POOL : 1];
     union {
-        alignas(8) uint8_t u_list[POOL];   // list of every entry (BUILD .. RANK)
+        alignas(8) uint8_t u_list[POOL];   // list of every entry (CAP = 64) / of every pair of entries (lp_cell) (BUILD .. RANK)
         uint8_t lk_slot[POOL];       // dead-lock scratch: slot of the record filed at each rank (LOCK2 .. FIN)
     };
     union {                          // (both < CAP: a list holds a vehicle at most once, the cycles claim <= one unit per member)
@@ -981,14 +994,31 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
     }
     static PVE_HD void ph_lists_b(int t, Sh &sh)
     {
+        int d = 0, k = 0, end = 0, np = 0;
         if (t < NL * 5) {
-            const int d = t / 5, k = t - d * 5;
+            d = t / 5; k = t - d * 5;
             const int base = d ? sh.pref[5 * d - 1] : 0;
             const int mine = t ? sh.pref[t - 1] : 0;
+            end = sh.pref[t];
             sh.segoff[d][k] = (int16_t)(mine - base);
-            if (k == 0) { sh.loff[d] = (int16_t)base; sh.nfin[d] = sh.pref[t] - base; }   // (own segment: all finite)
+            if (k == 0) { sh.loff[d] = (int16_t)base; sh.nfin[d] = end - base; }   // (own segment: all finite)
+            if (k == 4) np = (end - base + 1) >> 1;     // the last segment's lane: pairs of list d, an odd last entry alone
         }
         if (t == NL * 5) sh.loff[NL] = sh.pref[NL * 5 - 1];
+#if !PVE_DEVICE_CODE && defined(PVE_EMU_DIAG)
+        if (t == NL * 5 && CAP == 128) for (int q = 0; q < NL; q++) { const int n = sh.loff[q + 1] - sh.loff[q]; emu_diag_list_len[n < 63 ? n : 63]++; }
+#endif
+        if constexpr (!Sh::DIRECT) {
+            // RANK's pair index space: a second scan over the same 60 lanes (no LDS traffic), list d's first pair beside loff[d]
+#if PVE_DEVICE_CODE
+            const int pin = wave_incl_scan(t, np, nullptr);
+#else
+            if (t == 0) sh.emu_scan = 0;
+            const int pin = wave_incl_scan(t, np, &sh.emu_scan);
+#endif
+            if (t < NL * 5 && k == 4) sh.lpo()[d + 1] = end | (pin << 16);
+            if (t == 0) sh.lpo()[0] = 0;
+        }
     }
 
     // ============================================================== BUILD: every controlled vehicle files
@@ -1008,6 +1038,13 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
             return d1;
         }
     }
+    // Offsets of list d as BUILD and RANK read them: the plain loff[d] (CAP = 64), or loff[d] | first pair << 16 (lpo[]).
+    // u_list names the list of every ENTRY (CAP = 64) or of every PAIR of entries (RANK's index space; both entries of a
+    // pair store the same byte): lp_cell = the cell of the entry at position `in` of its list (entry e of the pool)
+    static PVE_HD int lp_word(const Sh &sh, int d) { if constexpr (Sh::DIRECT) return sh.loff[d]; else return sh.lpo()[d]; }
+    static PVE_HD int lp_lo(int w) { return Sh::DIRECT ? w : (w & 0xFFFF); }
+    static PVE_HD int lp_pair(int w) { return Sh::DIRECT ? 0 : (int)((unsigned)w >> 16); }
+    static PVE_HD int lp_cell(int w, int in, int e, int pgb) { return Sh::DIRECT ? e : lp_pair(w) - pgb + (in >> 1); }
     static PVE_HD void ph_build(const PVE_AS4 Const &c, int t, Sh &sh, Regs &r)
     {
         ph_build_prep(c, t, sh, r);
@@ -1038,11 +1075,13 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
         if (!r.dctl) return;
         const int sl = r.ds, lane = r.dlane;
         const double p = r.dp;
-        const int gb = GRP ? (int)sh.loff[d0] : 0;            // entry index of the group's first list
+        const int gw = GRP ? lp_word(sh, d0) : 0;
+        const int gb = lp_lo(gw), pgb = lp_pair(gw);          // entry index (and pair) of the group's first list
         const int q = t - sh.cstart[lane];                    // its rank among the controlled vehicles of its lane
         if (!GRP || (lane >= d0 && lane < d1)) {
-            const int e = sh.loff[lane] + q - gb;             // own lane: vd = p (ref :242-249)
-            sh.u_vd[e] = p; sh.u_slot[e] = (uint8_t)sl; sh.u_list[e] = (uint8_t)lane;
+            const int lw = lp_word(sh, lane);
+            const int e = lp_lo(lw) + q - gb;                 // own lane: vd = p (ref :242-249)
+            sh.u_vd[e] = p; sh.u_slot[e] = (uint8_t)sl; sh.u_list[lp_cell(lw, q, e, pgb)] = (uint8_t)lane;
         }
         if (lane % 3 == 2) return;                            // right turns conflict with nobody (ref :156)
         // three batches of independent LDS reads (lane tables, distance tables + list offsets), then the writes: written
@@ -1057,7 +1096,7 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             tA[k] = (&sh.tabA[0][0])[mk[k]]; tB[k] = (&sh.tabB[0][0])[mk[k]]; tC[k] = (&sh.tabC[0][0])[mk[k]];   // tab?[m][kk]
-            lo[k] = sh.loff[d[k]]; so[k] = sh.segoff[d[k]][kk[k] + 1];
+            lo[k] = lp_word(sh, d[k]); so[k] = sh.segoff[d[k]][kk[k] + 1];
         }
 #pragma unroll
         for (int k = 0; k < 4; k++) { PVE_PIN(tA[k]); PVE_PIN(tB[k]); PVE_PIN(tC[k]); PVE_PIN(lo[k]); PVE_PIN(so[k]); }
@@ -1065,9 +1104,9 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
         for (int k = 0; k < 4; k++) {
             const double delta = p - tA[k] + tB[k];                            // ref :733-803 (the relation is symmetric: kk =
             const double vd = (delta > 0) ? (tC[k] + delta) : INFINITY;        // our position inside lane2lane[d]); not chosen -> never sorted
-            const int e = lo[k] + so[k] + q - gb;
+            const int e = lp_lo(lo[k]) + so[k] + q - gb;
             if constexpr (GRP) { if (d[k] < d0 || d[k] >= d1) continue; }   // (another pass's list)
-            sh.u_vd[e] = vd; sh.u_slot[e] = (uint8_t)sl; sh.u_list[e] = (uint8_t)d[k];
+            sh.u_vd[e] = vd; sh.u_slot[e] = (uint8_t)sl; sh.u_list[lp_cell(lo[k], so[k] + q, e, pgb)] = (uint8_t)d[k];
             lds_add(&sh.nfin[d[k]], (delta > 0) ? 1 : 0);                       // (unconditional: no guarded block per entry)
         }
     }
@@ -1083,25 +1122,35 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
     // the whole run of equal distances in slot order (every later arrival rewrites the same values; the LDS executes
     // the operations of a wave in order, so the last fix-up is the last write).  A stale word that happens to carry the
     // stamp (left-over LDS contents) only sends an entry through the fix-up, which then files just itself.
+    //
+    // CAP >= 128: a lane ranks a PAIR of consecutive entries of one list (lane i takes pair i of the tick, lpo[] / u_list[]
+    // give its list and entries; the last entry of an odd list is a pair of one): every distance read from the list is
+    // counted against both, so the list is read once per pair instead of once per entry -- half the LDS reads for the same
+    // compares.  The two entries claim one after the other: when they share a distance the second one gets the first one's
+    // tag back and runs the fix-up, like any other later arrival.
     template <bool GRP = false>
     static PVE_HD void ph_rank(int t, Sh &sh, int salt = 0, int d0 = 0, int d1 = NL)
     {
-        const int gb = GRP ? (int)sh.loff[d0] : 0;        // (GRP: the lists [d0, d1) of this pass, entries relative to the first)
-        const int M = (GRP ? (int)sh.loff[d1] : (int)sh.loff[NL]) - gb;
-        const unsigned tag = Sh::DIRECT ? 0u : (((unsigned)sh.hd.ticks + (unsigned)salt * 0x9E37u) << 16);
+        if constexpr (Sh::DIRECT) ph_rank_entries(t, sh);
+        else ph_rank_pairs<GRP>(t, sh, salt, d0, d1);
+    }
+    // CAP = 64: one entry per lane, the sorted copy s_vd / s_slot, ties by counting the equal distances
+    static PVE_HD void ph_rank_entries(int t, Sh &sh)
+    {
+        const int M = sh.loff[NL];
         for (int e = t; e < M; e += CAP) {
             const int d = sh.u_list[e];
             const double vd = sh.u_vd[e];
             if (!(vd < INFINITY)) continue;               // not chosen (ref :259-270): not part of the list; the finite entries
                                                           // occupy the sorted positions [0, nfin[d])
-            const int lo = sh.loff[d] - gb, hi = sh.loff[d + 1] - gb;
+            const int lo = sh.loff[d], hi = sh.loff[d + 1];
             int pos = 0, eq = 0;
             int f = lo;
             for (; f + 8 <= hi; f += 8) {                 // 8 independent LDS reads per round
                 const double w0 = sh.u_vd[f], w1 = sh.u_vd[f + 1], w2 = sh.u_vd[f + 2], w3 = sh.u_vd[f + 3];
                 const double w4 = sh.u_vd[f + 4], w5 = sh.u_vd[f + 5], w6 = sh.u_vd[f + 6], w7 = sh.u_vd[f + 7];
                 pos += (w0 < vd) + (w1 < vd) + (w2 < vd) + (w3 < vd) + (w4 < vd) + (w5 < vd) + (w6 < vd) + (w7 < vd);
-                if (Sh::DIRECT) eq += (w0 == vd) + (w1 == vd) + (w2 == vd) + (w3 == vd) + (w4 == vd) + (w5 == vd) + (w6 == vd) + (w7 == vd);
+                eq += (w0 == vd) + (w1 == vd) + (w2 == vd) + (w3 == vd) + (w4 == vd) + (w5 == vd) + (w6 == vd) + (w7 == vd);
             }
             if (f < hi) {                                 // tail (< 8 entries): one more round of independent reads of
                 const int n = hi - f;                     // CONSECUTIVE entries; what lies behind the list is masked out (the
@@ -1110,25 +1159,69 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
 #pragma unroll
                 for (int k = 0; k < 7; k++) w[k] = uv[f + k];
 #pragma unroll
-                for (int k = 0; k < 7; k++) { pos += (k < n) & (w[k] < vd); if (Sh::DIRECT) eq += (k < n) & (w[k] == vd); }
+                for (int k = 0; k < 7; k++) { pos += (k < n) & (w[k] < vd); eq += (k < n) & (w[k] == vd); }
             }
             const int myslot = sh.u_slot[e];
             const int nown = sh.cstart[d + 1] - sh.cstart[d];                     // own-lane segment comes first
-            if (Sh::DIRECT) {
-                if (eq > 1)                               // exact vd ties: lower slot first
-                    for (f = lo; f < hi; f++) pos += (sh.u_vd[f] == vd && sh.u_slot[f] < myslot) ? 1 : 0;
-                sh.s_vd[lo + pos] = vd; sh.s_slot[lo + pos] = (uint8_t)myslot;
-                if (e - lo < nown) sh.mypos[myslot] = (uint8_t)pos;
-            } else {
+            if (eq > 1)                                   // exact vd ties: lower slot first
+                for (f = lo; f < hi; f++) pos += (sh.u_vd[f] == vd && sh.u_slot[f] < myslot) ? 1 : 0;
+            sh.s_vd[Sh::DIRECT ? lo + pos : 0] = vd; sh.s_slot[Sh::DIRECT ? lo + pos : 0] = (uint8_t)myslot;
+            if (e - lo < nown) sh.mypos[myslot] = (uint8_t)pos;
+        }
+    }
+    template <bool GRP>
+    static PVE_HD void ph_rank_pairs(int t, Sh &sh, int salt, int d0, int d1)
+    {
+        const int gw = GRP ? sh.lpo()[d0] : 0;            // (GRP: the lists [d0, d1) of this pass, entries and pairs relative
+        const int gb = lp_lo(gw), pgb = lp_pair(gw);      //  to the first)
+        const int NP = lp_pair(GRP ? sh.lpo()[d1] : sh.lpo()[NL]) - pgb;
+        const unsigned tag = ((unsigned)sh.hd.ticks + (unsigned)salt * 0x9E37u) << 16;
+        const double *uv = sh.u_vd;
+        for (int i = t; i < NP; i += CAP) {
+            const int d = sh.u_list[i];
+            const int lw = sh.lpo()[d];
+            const int lo = lp_lo(lw) - gb, hi = lp_lo(sh.lpo()[d + 1]) - gb;
+            const int e0 = lo + 2 * (i - (lp_pair(lw) - pgb));
+            const double vd0 = uv[e0];
+            double vd1 = uv[e0 + 1];                      // (an odd list's last pair: the next list's first entry, or up to one
+            if (e0 + 1 >= hi) vd1 = INFINITY;             //  double into `virdis` -- dropped here)
+            // not chosen (ref :259-270): not part of the list; the finite entries occupy the sorted positions [0, nfin[d])
+            if (!(vd0 < INFINITY) && !(vd1 < INFINITY)) continue;
+            int pos0 = 0, pos1 = 0;
+            int f = lo;
+            for (; f + 8 <= hi; f += 8) {                 // 8 independent LDS reads per round
+                const double w0 = uv[f], w1 = uv[f + 1], w2 = uv[f + 2], w3 = uv[f + 3];
+                const double w4 = uv[f + 4], w5 = uv[f + 5], w6 = uv[f + 6], w7 = uv[f + 7];
+                pos0 += (w0 < vd0) + (w1 < vd0) + (w2 < vd0) + (w3 < vd0) + (w4 < vd0) + (w5 < vd0) + (w6 < vd0) + (w7 < vd0);
+                pos1 += (w0 < vd1) + (w1 < vd1) + (w2 < vd1) + (w3 < vd1) + (w4 < vd1) + (w5 < vd1) + (w6 < vd1) + (w7 < vd1);
+            }
+            if (f < hi) {                                 // tail (< 8 entries): one more round of independent reads of
+                const int n = hi - f;                     // CONSECUTIVE entries; what lies behind the list is masked out (the
+                double w[7];                              // last list may run up to 6 doubles into `virdis`, the next member)
+#pragma unroll
+                for (int k = 0; k < 7; k++) w[k] = uv[f + k];
+#pragma unroll
+                for (int k = 0; k < 7; k++) { pos0 += (k < n) & (w[k] < vd0); pos1 += (k < n) & (w[k] < vd1); }
+            }
+            const int nown = sh.cstart[d + 1] - sh.cstart[d];                     // own-lane segment comes first
+#pragma unroll
+            for (int h = 0; h < 2; h++) {                 // the pair's claims, one after the other
+                const int e = e0 + h, pos = h ? pos1 : pos0;
+                const double vd = h ? vd1 : vd0;
+                if (!(vd < INFINITY)) continue;
+                const int myslot = sh.u_slot[e];
                 if (e - lo < nown) lds_store_relaxed(&sh.mypos[myslot], (uint8_t)pos);   // (before the claim -- released by it: a fix-up comes after it)
-                const unsigned old = lds_xchg(&sh.s_idx[Sh::DIRECT ? 0 : lo + pos], tag | (unsigned)e);
+                const unsigned old = lds_xchg(&sh.s_idx[lo + pos], tag | (unsigned)e);
                 if ((old & 0xFFFF0000u) == tag) {         // somebody with the same distance was here first (or a stale word)
+#if !PVE_DEVICE_CODE && defined(PVE_EMU_DIAG)
+                    emu_diag_ties[(h == 1 && vd0 == vd1) ? 0 : 1]++;
+#endif
                     for (f = lo; f < hi; f++) {
-                        if (!(sh.u_vd[f] == vd)) continue;
+                        if (!(uv[f] == vd)) continue;
                         const int sf = sh.u_slot[f];
                         int rk = 0;
-                        for (int g = lo; g < hi; g++) rk += (sh.u_vd[g] == vd && sh.u_slot[g] < sf) ? 1 : 0;
-                        lds_store_relaxed(&sh.s_idx[Sh::DIRECT ? 0 : lo + pos + rk], tag | (unsigned)f);
+                        for (int g = lo; g < hi; g++) rk += (uv[g] == vd && sh.u_slot[g] < sf) ? 1 : 0;
+                        lds_store_relaxed(&sh.s_idx[lo + pos + rk], tag | (unsigned)f);
                         if (f - lo < nown) lds_store_relaxed(&sh.mypos[sf], (uint8_t)(pos + rk));
                     }
                 }
