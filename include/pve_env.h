@@ -389,6 +389,61 @@ int pve_replay_append(pve_handle h, const pve_replay *rp, const float *records /
 int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t n_batches, float *rows, float *act7,
                       float *target, int64_t *seq);
 
+/* LEARNER STEP on the device: what the reference runs on a minibatch behind getBatch (main.py:48-84 `train_agent_seq`:
+ * model_agent_maddpg.py:85-118 `train_critic`, then `train_actor`, then main.py:19-33 the soft updates of both targets).
+ * Additive within ABI 9: two new symbols and one new struct, nothing existing changes, PVE_ABI_VERSION stays 9; a binding
+ * detects an older library by the missing symbols.  The arithmetic -- every order of summation, Adam, the tanh -- is stated once
+ * in csrc/pve_learn.h, which a host compiler builds as well; the kernel computes that, bit for bit, whatever block_threads.
+ *
+ * `params` is a caller-owned DEVICE block of PVE_LEARNER_N_FLOATS float32.  Segments (float offsets, each 16-byte aligned):
+ *   PVE_LEARNER_ACTOR / _CRITIC / _TARGET_ACTOR / _TARGET_CRITIC   the four networks, in exactly the layouts pve_set_actor and
+ *       pve_set_target_networks take: pve_set_actor(h, params + PVE_LEARNER_ACTOR) installs the new policy with no host copy
+ *   PVE_LEARNER_M_ACTOR / _V_ACTOR / _M_CRITIC / _V_CRITIC          Adam's moments
+ *   PVE_LEARNER_POWERS   beta1^t, beta2^t of the actor's optimizer, then of the critic's
+ *   PVE_LEARNER_STEPS    int32: steps taken (+ 3 reserved words)
+ *   PVE_LEARNER_GRAD     the gradients of the latest step: critic [6841] (padded to 6844), then actor [6393]
+ * pve_learner_init (main.py:203-204) copies the networks in (DEVICE pointers; a NULL target = a copy of the online network),
+ * zeroes moments, count and gradients and sets the powers to beta1, beta2.
+ * pve_learner_step runs n_batches steps in sequence in ONE launch of one workgroup, on
+ *   rows float32 [n_batches][batch][28], act7 float32 [n_batches][batch][7], target float32 [n_batches][batch]
+ * (what pve_replay_sample writes).  Per step: 1. critic_loss = mean((target - Q)^2), Adam on the critic; 2. actor_loss =
+ * -mean(Q(s, [actor(s), act7[1..6]])) with the UPDATED critic, gradients with respect to the actor only, Adam on the actor;
+ * 3. target = c1 * online + c2 * target for both, c1 = float32(1.0 - (double)tau), c2 = float32(tau).  Adam is TF 1.x ApplyAdam
+ * in float32 (csrc/pve_learn.h).  losses [n_batches][2] = critic, actor loss of each step, or NULL; grads
+ * [n_batches][6841 + 6393] = the gradients each step applied, critic then actor, or NULL.  PVE_LEARN_CRITIC_ONLY skips 2. and the
+ * actor's soft update (actor loss and gradients are reported as 0).
+ * NOT reproduced: td_error / update_priority (main.py:76-79; dead with rand_s = True) and the summaries.  The reference assigns
+ * self.critic_lr after the optimizer is built, which changes nothing there; here both learning rates are read on every call.
+ * block_threads: 0 = 1024; else a multiple of 64 up to 1024 (same results).
+ * Errors (PVE_ERR_INVALID): null pointers, batch < 1, n_batches < 1, batch * n_batches > 2^31 - 1, params / rows / networks not
+ * 16-byte aligned (the others: 4), learning rates, epsilon or tau not finite, tau outside [0, 1], beta outside [0, 1), a bad
+ * block_threads, a backend without the kernel.  Both calls are asynchronous on the handle's stream and need no pve_reset. */
+#define PVE_LEARNER_ACTOR 0
+#define PVE_LEARNER_CRITIC 6396
+#define PVE_LEARNER_TARGET_ACTOR 13240
+#define PVE_LEARNER_TARGET_CRITIC 19636
+#define PVE_LEARNER_M_ACTOR 26480
+#define PVE_LEARNER_V_ACTOR 32876
+#define PVE_LEARNER_M_CRITIC 39272
+#define PVE_LEARNER_V_CRITIC 46116
+#define PVE_LEARNER_POWERS 52960
+#define PVE_LEARNER_STEPS 52964
+#define PVE_LEARNER_GRAD 52968
+#define PVE_LEARNER_N_FLOATS 66208
+#define PVE_LEARN_CRITIC_ONLY 0x1
+typedef struct pve_learner {
+    float *params;                /* DEVICE [PVE_LEARNER_N_FLOATS] */
+    float actor_lr, critic_lr;    /* reference: 1e-4, 1e-3 */
+    float beta1, beta2, epsilon;  /* tf.train.AdamOptimizer's defaults: 0.9, 0.999, 1e-8 */
+    float tau;                    /* weight of the OLD target (main.py:30); reference 0.998 */
+    int32_t flags;                /* PVE_LEARN_* */
+    int32_t block_threads;
+} pve_learner;
+int pve_learner_init(pve_handle h, const pve_learner *lrn, const float *actor, const float *critic,
+                     const float *target_actor /* NULL = actor */, const float *target_critic /* NULL = critic */);
+int pve_learner_step(pve_handle h, const pve_learner *lrn, const float *rows, const float *act7, const float *target,
+                     int64_t batch, int64_t n_batches, float *losses /* or NULL */, float *grads /* or NULL */);
+
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly
  * pve_step_all() with

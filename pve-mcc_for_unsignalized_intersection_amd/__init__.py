@@ -4,5 +4,7 @@ behind a C ABI (include/pve_env.h -> libpveenv.so)."""
 from ._capi import PveError, load_library  # noqa: F401
 from .batched import BatchedIntersections, PipelinedIntersections  # noqa: F401
 from .replay import ReplayMemory, ReplayModel  # noqa: F401
+from .learner import Learner, LearnerModel  # noqa: F401
 
-__all__ = ["BatchedIntersections", "PipelinedIntersections", "PveError", "ReplayMemory", "ReplayModel", "load_library"]
+__all__ = ["BatchedIntersections", "Learner", "LearnerModel", "PipelinedIntersections", "PveError", "ReplayMemory", "ReplayModel",
+           "load_library"]

@@ -76,6 +76,11 @@ class PveReplay(C.Structure):
                 ("block_threads", C.c_int32)]
 
 
+class PveLearner(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("epsilon", C.c_float), ("tau", C.c_float), ("flags", C.c_int32), ("block_threads", C.c_int32)]
+
+
 class PveVehicle(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("p", "v", "a", "jerk", "jerk_sum", "vir_dis", "closer_p")] + \
                [(n, C.c_int32) for n in ("lane", "j", "id", "vnum", "seq_in_lane", "control", "finish", "done",
@@ -98,7 +103,7 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_step_all_actor", "pve_debug_traffic_probe", "pve_set_intentions", "pve_step_many", "pve_set_actor",
            "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise",
            "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather",
-           "pve_replay_reset", "pve_replay_append", "pve_replay_sample")
+           "pve_replay_reset", "pve_replay_append", "pve_replay_sample", "pve_learner_init", "pve_learner_step")
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -139,6 +144,8 @@ def _declare(L):
     L.pve_replay_reset.argtypes = [vp, C.POINTER(PveReplay)]
     L.pve_replay_append.argtypes = [vp, C.POINTER(PveReplay), vp, vp, C.c_int64]
     L.pve_replay_sample.argtypes = [vp, C.POINTER(PveReplay), C.c_int64, C.c_int64, vp, vp, vp, vp]
+    L.pve_learner_init.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, vp]
+    L.pve_learner_step.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
     for name in EXPORTS:

@@ -48,6 +48,10 @@
 //     static int   launch_replay_sample(const pve::ReplayArgs &, long long batch, long long n_batches, float *rows, float *act7,
 //                                       float *target, long long *seq, int block_threads, void *stream, std::string &err);
 //                                                // optional, both or none: pve_replay_reset / _append / _sample (csrc/pve_replay.h)
+//     static int   launch_learner_init(float *params, const float *actor, const float *critic, const float *target_actor,
+//                                      const float *target_critic, float beta1, float beta2, void *stream, std::string &err);
+//     static int   launch_learner_step(const pve::LearnCtx &, int block_threads, void *stream, std::string &err);
+//                                                // optional, both or none: pve_learner_init / pve_learner_step (csrc/pve_learn.h)
 //   };
 //
 // pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
@@ -255,6 +259,26 @@ template <class B> struct backend_replay<B, decltype((void)&B::launch_replay_sam
         return B::launch_replay_sample(A, batch, n_batches, rows, act7, target, seq, block, stream, err);
     }
 };
+// The learner step (pve_learner_init / pve_learner_step) needs the kernels behind Backend::launch_learner_init /
+// launch_learner_step (detected by the second).  A backend without them exports the entry points all the same; they validate
+// their arguments and then refuse with PVE_ERR_INVALID.
+template <class B, class = void> struct backend_learner {
+    static constexpr bool value = false;
+    static int init(float *, const float *, const float *, const float *, const float *, float, float, void *, std::string &) { return -1; }
+    static int step(const LearnCtx &, int, void *, std::string &) { return -1; }
+};
+template <class B> struct backend_learner<B, decltype((void)&B::launch_learner_step)> {
+    static constexpr bool value = true;
+    static int init(float *P, const float *a, const float *c, const float *ta, const float *tc, float beta1, float beta2, void *stream,
+                    std::string &err) { return B::launch_learner_init(P, a, c, ta, tc, beta1, beta2, stream, err); }
+    static int step(const LearnCtx &C, int block, void *stream, std::string &err) { return B::launch_learner_step(C, block, stream, err); }
+};
+static_assert(LB_ACTOR == PVE_LEARNER_ACTOR && LB_CRITIC == PVE_LEARNER_CRITIC && LB_TACTOR == PVE_LEARNER_TARGET_ACTOR &&
+              LB_TCRITIC == PVE_LEARNER_TARGET_CRITIC && LB_M_ACTOR == PVE_LEARNER_M_ACTOR && LB_V_ACTOR == PVE_LEARNER_V_ACTOR &&
+              LB_M_CRITIC == PVE_LEARNER_M_CRITIC && LB_V_CRITIC == PVE_LEARNER_V_CRITIC && LB_POWERS == PVE_LEARNER_POWERS &&
+              LB_STEPS == PVE_LEARNER_STEPS && LB_GRAD == PVE_LEARNER_GRAD && LB_TOTAL == PVE_LEARNER_N_FLOATS &&
+              LRN_ACTOR_W == PVE_ACTOR_N_WEIGHTS && LRN_CRITIC_W == PVE_CRITIC_N_WEIGHTS && LEARN_CRITIC_ONLY == PVE_LEARN_CRITIC_ONLY,
+              "the learner's block layout (include/pve_env.h PVE_LEARNER_*)");
 extern "C" {
 
 int pve_abi_version(void) { return PVE_ABI_VERSION; }
@@ -681,6 +705,68 @@ int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t
     if (backend_replay<Backend>::sample(A, (long long)batch, (long long)n_batches, rows, act7, target, (long long *)seq, rp->block_threads,
                                         h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_replay_sample: " + err);
+    return PVE_OK;
+}
+
+// pve_learner -> LearnHyper, with the checks the two entry points share
+static int learner_args(pve_handle h, const pve_learner *lrn, const char *who, LearnHyper &H)
+{
+    const std::string w(who);
+    if (!h || !lrn) return fail(PVE_ERR_INVALID, w + ": null argument");
+    if (!lrn->params) return fail(PVE_ERR_INVALID, w + ": null params");
+    if ((uintptr_t)lrn->params & 15) return fail(PVE_ERR_INVALID, w + ": params must be 16-byte aligned");
+    const float big = 3.4028234663852886e38f;
+    const float fin[4] = {lrn->actor_lr, lrn->critic_lr, lrn->epsilon, lrn->tau};
+    for (int k = 0; k < 4; k++)
+        if (!(fin[k] >= -big && fin[k] <= big)) return fail(PVE_ERR_INVALID, w + ": actor_lr, critic_lr, epsilon and tau must be finite");
+    if (!(lrn->tau >= 0.f && lrn->tau <= 1.f)) return fail(PVE_ERR_INVALID, w + ": tau must lie in [0, 1]");
+    if (!(lrn->beta1 >= 0.f && lrn->beta1 < 1.f) || !(lrn->beta2 >= 0.f && lrn->beta2 < 1.f))
+        return fail(PVE_ERR_INVALID, w + ": beta1 and beta2 must lie in [0, 1)");
+    if (lrn->flags & ~PVE_LEARN_CRITIC_ONLY) return fail(PVE_ERR_INVALID, w + ": unknown flags");
+    if (lrn->block_threads < 0 || lrn->block_threads > 1024 || lrn->block_threads % 64)
+        return fail(PVE_ERR_INVALID, w + ": block_threads must be 0 or a multiple of 64 up to 1024");
+    H.actor_lr = lrn->actor_lr; H.critic_lr = lrn->critic_lr; H.beta1 = lrn->beta1; H.beta2 = lrn->beta2; H.epsilon = lrn->epsilon;
+    H.tau = lrn->tau; H.flags = lrn->flags;
+    return PVE_OK;
+}
+
+int pve_learner_init(pve_handle h, const pve_learner *lrn, const float *actor, const float *critic, const float *target_actor,
+                     const float *target_critic)
+{
+    LearnHyper H;
+    const int rc = learner_args(h, lrn, "pve_learner_init", H);
+    if (rc != PVE_OK) return rc;
+    if (!actor || !critic) return fail(PVE_ERR_INVALID, "pve_learner_init: null actor or critic");
+    if (((uintptr_t)actor | (uintptr_t)critic | (uintptr_t)target_actor | (uintptr_t)target_critic) & 15)
+        return fail(PVE_ERR_INVALID, "pve_learner_init: the networks must be 16-byte aligned");
+    if (!backend_learner<Backend>::value) return fail(PVE_ERR_INVALID, "pve_learner_init: this backend has no learner kernels");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_learner<Backend>::init(lrn->params, actor, critic, target_actor ? target_actor : actor, target_critic ? target_critic : critic,
+                                       H.beta1, H.beta2, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_learner_init: " + err);
+    return PVE_OK;
+}
+
+int pve_learner_step(pve_handle h, const pve_learner *lrn, const float *rows, const float *act7, const float *target, int64_t batch,
+                     int64_t n_batches, float *losses, float *grads)
+{
+    LearnCtx C;
+    memset(&C, 0, sizeof(C));
+    const int rc = learner_args(h, lrn, "pve_learner_step", C.H);
+    if (rc != PVE_OK) return rc;
+    if (!rows || !act7 || !target) return fail(PVE_ERR_INVALID, "pve_learner_step: null rows, act7 or target");
+    if (batch < 1) return fail(PVE_ERR_INVALID, "pve_learner_step: batch must be >= 1");
+    if (n_batches < 1 || n_batches > 0x7fffffffLL / batch)
+        return fail(PVE_ERR_INVALID, "pve_learner_step: n_batches must be >= 1 and batch * n_batches <= 2^31 - 1");
+    if (((uintptr_t)rows & 15) || (((uintptr_t)act7 | (uintptr_t)target | (uintptr_t)losses | (uintptr_t)grads) & 3))
+        return fail(PVE_ERR_INVALID, "pve_learner_step: rows must be 16-byte aligned, act7, target, losses and grads 4-byte aligned");
+    if (!backend_learner<Backend>::value) return fail(PVE_ERR_INVALID, "pve_learner_step: this backend has no learner kernels");
+    C.P = lrn->params; C.rows = rows; C.act7 = act7; C.target = target; C.losses = losses; C.grads = grads;
+    C.batch = (int)batch; C.n_batches = (int)n_batches;
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_learner<Backend>::step(C, lrn->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_learner_step: " + err);
     return PVE_OK;
 }
 

@@ -21,6 +21,7 @@
 #include "pve_critic.h"
 #include "pve_nstep.h"
 #include "pve_replay.h"
+#include "pve_learn.h"
 
 using namespace pve;
 
@@ -982,6 +983,52 @@ __global__ __launch_bounds__(64) void k_reset(const Const c_arg, const Params P_
     if (env < P.n_envs) reset_env<CAP>(c, P, env, cap_ticks);
 }
 
+// ------------------------------------------------------------------ the learner step (csrc/pve_learn.h)
+// k_learner_step: ONE workgroup runs n_batches steps in sequence.  The work items of every phase of learn_steps are dealt to the
+// threads (item i to thread i mod blockDim.x), one workgroup barrier closes each phase: no grid-wide barrier, no flag, no wait on
+// another workgroup, every loop bounded by the arguments.  Which thread computes an item changes no bit of it: the orders of
+// pve_learn.h are orders WITHIN an item.  LDS holds the tape of one sub-block of rows (odd row stride: the rows of neighbouring
+// lanes fall into different banks) and the step's running sums.  Weights, moments, targets and gradients stay in the block in
+// global memory (52 KB of online weights: resident in the CU's L1 / L2; measured faster than a copy in LDS with half the rows
+// per sub-block); what one thread writes there another reads only behind a workgroup barrier, and one workgroup
+// shares one L1.  A gradient is accumulated and applied by the same thread.
+struct LearnWg {
+    int tid, nt;
+    template <class F> PVE_HD void forall(int n, F f) const
+    {
+        for (int i = tid; i < n; i += nt) f(i);
+#if defined(__HIP_DEVICE_COMPILE__)
+        __syncthreads();
+#endif
+    }
+};
+constexpr int LEARN_LDS_FLOATS = LEARN_TAPE + LEARN_SCALARS;
+static_assert(LEARN_LDS_FLOATS * 4 <= 160 * 1024, "one workgroup's LDS on gfx950");
+static_assert((LEARN_SUB_1 - 1) * LEARN_STRIDE_1 + T_NET <= LEARN_TAPE && (LEARN_SUB_2 - 1) * LEARN_STRIDE_2 + 2 * T_NET <= LEARN_TAPE,
+              "the tape of a sub-block stays inside its LDS region");
+__global__ __launch_bounds__(1024) void k_learner_step(LearnCtx C)
+{
+    extern __shared__ __attribute__((aligned(16))) float learn_s[];
+    if (blockIdx.x != 0) return;
+    C.tape = learn_s; C.S = learn_s + LEARN_TAPE;
+    learn_steps(LearnWg{(int)threadIdx.x, (int)blockDim.x}, C);
+}
+
+// pve_learner_init: the four networks into the block, moments / count / gradients zeroed, the powers set to beta1, beta2
+__global__ __launch_bounds__(256) void k_learner_init(float *__restrict__ P, const float *__restrict__ actor, const float *__restrict__ critic,
+                                                      const float *__restrict__ tactor, const float *__restrict__ tcritic, float beta1, float beta2)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < LB_TOTAL; i += gridDim.x * blockDim.x) {
+        float v = 0.f;
+        if (i < LB_CRITIC) { if (i - LB_ACTOR < LRN_ACTOR_W) v = actor[i - LB_ACTOR]; }
+        else if (i < LB_TACTOR) { if (i - LB_CRITIC < LRN_CRITIC_W) v = critic[i - LB_CRITIC]; }
+        else if (i < LB_TCRITIC) { if (i - LB_TACTOR < LRN_ACTOR_W) v = tactor[i - LB_TACTOR]; }
+        else if (i < LB_M_ACTOR) { if (i - LB_TCRITIC < LRN_CRITIC_W) v = tcritic[i - LB_TCRITIC]; }
+        else if (i >= LB_POWERS && i < LB_STEPS) v = ((i - LB_POWERS) & 1) ? beta2 : beta1;
+        P[i] = v;
+    }
+}
+
 static std::string hip_err(const char *what, hipError_t e)
 {
     return std::string(what) + ": " + hipGetErrorString(e);
@@ -1425,6 +1472,32 @@ struct Backend {
         hipLaunchKernelGGL(k_replay_sample, dim3((unsigned)((n_total + block - 1) / block)), dim3(block), replay_sample_lds(block), s, A, batch,
                            n_total, rows, act7, target, seq);
         hipLaunchKernelGGL(k_replay_sample_commit, dim3(1), dim3(64), 0, s, A, batch, n_batches);
+        return check_launch(err);
+    }
+    // pve_learner_init / pve_learner_step: one workgroup; 153 KB of dynamic LDS need the function attribute (once per device)
+    static int launch_learner_init(float *P, const float *actor, const float *critic, const float *tactor, const float *tcritic,
+                                   float beta1, float beta2, void *stream, std::string &err)
+    {
+        return launch(k_learner_init, (LB_TOTAL + 255) / 256, 256, stream, err, P, actor, critic, tactor, tcritic, beta1, beta2);
+    }
+    static int launch_learner_step(const LearnCtx &C, int block_threads, void *stream, std::string &err)
+    {
+        constexpr size_t lds = sizeof(float) * LEARN_LDS_FLOATS;
+        static std::mutex mu;
+        static bool attr_set[64] = {};
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) { err = hip_err("hipGetDevice", e); return -1; }
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+                e = hipFuncSetAttribute((const void *)k_learner_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) { err = hip_err("hipFuncSetAttribute", e); return -1; }
+                if (dev >= 0 && dev < 64) attr_set[dev] = true;
+            }
+        }
+        const int block = block_threads > 0 ? block_threads : 1024;
+        hipLaunchKernelGGL(k_learner_step, dim3(1), dim3(block), lds, (hipStream_t)stream, C);
         return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)
