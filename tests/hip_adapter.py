@@ -1,8 +1,6 @@
 """Adapters that drive the product's BatchedIntersections (real HIP library on a GPU, or the CPU
 test emulator of the same kernels) and emit the canonical tick records of oracle/record.py."""
-import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import torch
@@ -10,18 +8,17 @@ import torch
 import pve_mcc_amd
 from pve_mcc_amd import _capi
 from pve_mcc_amd.batched import ALL_OUTPUTS, BatchedIntersections
+from tests import native
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-EMU_DIR = os.path.join(ROOT, "tests", "emu")
 _emu = None
 
 
 def emulator_lib():
     """CPU test emulator of the HIP kernels (tests/emu). Test infrastructure only."""
     global _emu
-    if _emu is None:
-        subprocess.check_call(["make", "-C", EMU_DIR, "-s", "libpveenv_emu.so"])
-        _emu = _capi._declare(C.CDLL(os.path.join(EMU_DIR, "libpveenv_emu.so")))
+    if _emu is None:                       # (rank_pairs_scenarios.diag_emulator() swaps _emu)
+        _emu = native.load_emulator("emu", "libpveenv_emu.so")
     return _emu
 
 

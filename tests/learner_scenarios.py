@@ -5,17 +5,16 @@ from tests/golden/actor_66.npz."""
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 
 from pve_mcc_amd import learner as LN
 from pve_mcc_amd.critic import KEYS
+from tests import native
 from tests.critic_scenarios import load_critic_golden
 from tests.parity_util import GOLDEN_DIR
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-SHIM_DIR = os.path.join(ROOT, "tests", "learner_host")
 HYPER = dict(actor_lr=1e-4, critic_lr=1e-3, beta1=0.9, beta2=0.999, epsilon=1e-8, tau=0.998)       # the reference's run
 
 # ---------------------------------------------------------------------------------- the bar of "the header against the semantics"
@@ -35,12 +34,13 @@ def bits32(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-@functools.lru_cache(maxsize=None)
 def shim(name="liblearner_host.so"):
-    """csrc/pve_learn.h compiled by g++ (tests/learner_host), built on demand like the emulator library.
+    """csrc/pve_learn.h compiled by g++ (tests/learner_host), built and loaded by tests/native.py.
     "liblearner_host_sub.so" is the same header with sub-blocks of 7 / 5 rows instead of 64 / 32."""
-    subprocess.check_call(["make", "-C", SHIM_DIR, "-s", name])
-    L = C.CDLL(os.path.join(SHIM_DIR, name))
+    return native.load("learner_host", name, _signatures)
+
+
+def _signatures(L):
     vp = C.c_void_p
     L.learner_host_layout.restype = None
     L.learner_host_layout.argtypes = [vp]

@@ -10,12 +10,12 @@ import ctypes as C
 import functools
 import math
 import os
-import subprocess
 
 import mpmath
 import numpy as np
 
 from pve_mcc_amd._capi import PveConfig
+from tests import native
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 PROBE_DIR = os.path.join(ROOT, "tests", "math_probe")
@@ -39,20 +39,11 @@ class ProbeArgs(C.Structure):
     _fields_ = [("n", C.c_longlong), ("inp", C.c_void_p * 6), ("out", C.c_void_p * 3), ("k", C.c_int * 4)]
 
 
-def sources():
-    return [os.path.join(PROBE_DIR, f) for f in ("pve_math_probe.hip", "Makefile")] + \
-           [os.path.join(CSRC_DIR, f) for f in ("Makefile", "pve_tick_core.h", "pve_tick_geo.h", "pve_actor.h", "pve_types.h", "pve_host.h")] + \
-           [os.path.join(ROOT, "tests", "emu", "Makefile")]
-
-
 def build(kind, always_make=True):
-    """`make` the flavour (a no-op when it is up to date).  always_make=False: only if the object is missing or older than its
-    sources (the GPU module: the device object usually travels with the tree).  A failure to build is an error, never a skip."""
-    path = os.path.join(PROBE_DIR, LIB[kind])
-    if always_make or not os.path.exists(path) or os.path.getmtime(path) < max(os.path.getmtime(s) for s in sources()):
-        subprocess.check_call(["make", "-C", PROBE_DIR, "-s", LIB[kind]])
-    assert os.path.exists(path), path
-    return path
+    """`make` the flavour through tests/native.py (a no-op when it is up to date) -> its path.  always_make=False once meant
+    "only if the object is missing or older than its sources"; that is `make`'s own question, so both values ask `make` now
+    and the argument only keeps the callers' spelling.  A failure to build is an error, never a skip."""
+    return native.build("math_probe", LIB[kind])
 
 
 def make_cfg(**kw):
@@ -67,7 +58,7 @@ class Probe:
 
     def __init__(self, kind, always_make=True):
         self.kind = kind
-        self.lib = C.CDLL(build(kind, always_make))
+        self.lib = native.load("math_probe", LIB[kind])             # (always_make: see build)
         assert self.lib.pve_probe_is_device() == (1 if kind == "hip" else 0)
 
     def raw(self, name, ins, outs, cfg=None, k=(), n=None):

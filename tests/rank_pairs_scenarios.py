@@ -17,31 +17,20 @@ of the queue kernel on the GPU, the same phase bodies on the emulator (PVE_EMU_H
 """
 import collections
 import contextlib
-import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 
 from oracle.record import close
 from tests import bounded_scenarios as B
-from tests import scenarios
+from tests import native, scenarios
 from tests.hip_adapter import _np, state_snapshot
-
-DIAG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu_diag")
-_diag = None
 
 
 def diag_emulator_lib():
     """The CPU test emulator built with RANK's counters (PVE_EMU_DIAG) and the RANK probe (tests/emu_diag): the very sources of
     tests/emu, one more translation unit around them."""
-    global _diag
-    if _diag is None:
-        from pve_mcc_amd import _capi
-        subprocess.check_call(["make", "-C", DIAG_DIR, "-s", "libpveenv_emu_diag.so"])
-        _diag = _capi._declare(C.CDLL(os.path.join(DIAG_DIR, "libpveenv_emu_diag.so")))
-    return _diag
+    return native.load_emulator("emu_diag", "libpveenv_emu_diag.so")
 
 
 @contextlib.contextmanager

@@ -4,32 +4,29 @@ the noise are checked in tests/test_gpu_action_noise.py."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from pve_mcc_amd import PveError, _capi, noise
+from tests import native
 from tests.hip_adapter import _np, emulator_lib, make_batch
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-SHIM_DIR = os.path.join(ROOT, "tests", "noise_host")
-_shim = None
+
+
+def _signatures(L):
+    L.noise_philox.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.noise_gauss_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+    L.noise_z_many.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+    L.noise_apply.argtypes = [C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_int32, C.c_uint32]
+    L.noise_apply.restype = C.c_double
+    return L
 
 
 def shim():
-    """csrc/pve_noise.h compiled by g++ (tests/noise_host), built on demand like the emulator library."""
-    global _shim
-    if _shim is None:
-        subprocess.check_call(["make", "-C", SHIM_DIR, "-s", "libnoise_host.so"])
-        L = C.CDLL(os.path.join(SHIM_DIR, "libnoise_host.so"))
-        L.noise_philox.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.noise_gauss_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
-        L.noise_z_many.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
-        L.noise_apply.argtypes = [C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_int32, C.c_uint32]
-        L.noise_apply.restype = C.c_double
-        _shim = L
-    return _shim
+    """csrc/pve_noise.h compiled by g++ (tests/noise_host), built and loaded by tests/native.py."""
+    return native.load("noise_host", "libnoise_host.so", _signatures)
 
 
 def shim_gauss(w0, w1):

@@ -2,30 +2,19 @@
 frozen 64 / 128 emulator (tests/emu) still refuses it, and the phase bodies at 256 slots -- run by the wide emulator
 (tests/emu_wide, the 256-slot kernels' phase order) -- follow the oracle on a stream that peaks far above 128 vehicles.
 The `-m gpu` twin is test_gpu_capacity256.py."""
-import ctypes as C
-import os
-import subprocess
-
 import pytest
 
 from pve_mcc_amd import _capi
 from pve_mcc_amd._capi import PveError
 from pve_mcc_amd.arrivals import synthetic_arrivals
 from tests import cap256_scenarios as cs
-from tests import hip_adapter, scenarios
+from tests import hip_adapter, native, scenarios
 from tests.hip_adapter import make_batch
 from tests.parity_util import GoldenCase, replay_case
 
-EMU_WIDE_DIR = os.path.join(hip_adapter.ROOT, "tests", "emu_wide")
-_wide = None
-
 
 def wide_lib():
-    global _wide
-    if _wide is None:
-        subprocess.check_call(["make", "-C", EMU_WIDE_DIR, "-s", "libpveenv_emu_wide.so"])
-        _wide = _capi._declare(C.CDLL(os.path.join(EMU_WIDE_DIR, "libpveenv_emu_wide.so")))
-    return _wide
+    return native.load_emulator("emu_wide", "libpveenv_emu_wide.so")
 
 
 @pytest.fixture

@@ -8,31 +8,28 @@ evaluation in another order lies within one spread of the real value, hence with
 result itself rounds to half an ulp of |Q| <= 148: 7.6e-6, well inside)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from pve_mcc_amd import PveError, _capi, critic
+from tests import native
 from tests.critic_scenarios import load_critic_golden
 from tests.hip_adapter import _np, emulator_lib, make_batch
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-SHIM_DIR = os.path.join(ROOT, "tests", "critic_host")
-_shim = None
+
+
+def _signatures(L):
+    L.critic_canonical_many.argtypes = [C.c_void_p] * 4 + [C.c_longlong]
+    L.bootstrap_canonical_many.argtypes = [C.c_void_p] * 5 + [C.c_longlong]
+    return L
 
 
 def shim():
-    """csrc/pve_critic.h compiled by g++ (tests/critic_host), built on demand like the emulator library."""
-    global _shim
-    if _shim is None:
-        subprocess.check_call(["make", "-C", SHIM_DIR, "-s", "libcritic_host.so"])
-        L = C.CDLL(os.path.join(SHIM_DIR, "libcritic_host.so"))
-        L.critic_canonical_many.argtypes = [C.c_void_p] * 4 + [C.c_longlong]
-        L.bootstrap_canonical_many.argtypes = [C.c_void_p] * 5 + [C.c_longlong]
-        _shim = L
-    return _shim
+    """csrc/pve_critic.h compiled by g++ (tests/critic_host), built and loaded by tests/native.py."""
+    return native.load("critic_host", "libcritic_host.so", _signatures)
 
 
 def flat_actor(w):

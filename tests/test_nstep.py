@@ -4,38 +4,33 @@ through a g++ host shim (tests/nstep_host), hand-made trajectories (tests/nstep_
 and the two C ABI entry points on the emulator (which has no n-step kernels and must say so).  The kernels are checked in
 tests/test_gpu_nstep.py.  Everything here is exact: targets are compared as float64 bit patterns."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 from pve_mcc_amd import PveError, _capi, nstep
+from tests import native
 from tests import nstep_scenarios as S
 from tests.hip_adapter import _np, emulator_lib, make_batch
 from tests.parity_util import GOLDEN_DIR
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-SHIM_DIR = os.path.join(ROOT, "tests", "nstep_host")
 GAMMA0 = float(np.tanh(6.0 / 12.0) * 0.9)            # main.py:227 at epoch 0
-_shim = None
 
 
 def bits(x):
     return np.ascontiguousarray(np.asarray(x, np.float64)).view(np.uint64)
 
 
+def _signatures(L):
+    L.nstep_scan_host.restype = C.c_longlong
+    L.nstep_scan_host.argtypes = [C.c_double] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8
+    return L
+
+
 def shim():
-    """csrc/pve_nstep.h compiled by g++ (tests/nstep_host), built on demand like the emulator library."""
-    global _shim
-    if _shim is None:
-        subprocess.check_call(["make", "-C", SHIM_DIR, "-s", "libnstep_host.so"])
-        L = C.CDLL(os.path.join(SHIM_DIR, "libnstep_host.so"))
-        L.nstep_scan_host.restype = C.c_longlong
-        L.nstep_scan_host.argtypes = [C.c_double] + [C.c_int] * 6 + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 8
-        _shim = L
-    return _shim
+    """csrc/pve_nstep.h compiled by g++ (tests/nstep_host), built and loaded by tests/native.py."""
+    return native.load("nstep_host", "libnstep_host.so", _signatures)
 
 
 def shim_scan(cur, gamma, window=13, prev=None, obs_first=None, q=None, tail=False):

@@ -4,35 +4,32 @@ its own specification (bijection, independence of how the j range is cut, unifor
 kernels are held to ReplayModel in tests/test_gpu_replay.py.  Everything is exact."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 from pve_mcc_amd import PveError, ReplayMemory, ReplayModel, _capi, replay
+from tests import native
 from tests import replay_scenarios as S
 from tests.hip_adapter import emulator_lib, make_batch
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-SHIM_DIR = os.path.join(ROOT, "tests", "replay_host")
 REF_DIR = "/root/reference"
-_shim = None
+
+
+def _signatures(L):
+    L.replay_half_bits_host.argtypes = [C.c_uint32]
+    L.replay_perm_host.restype = None
+    L.replay_perm_host.argtypes = [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_longlong, C.c_void_p]
+    L.replay_append_host.restype = C.c_longlong
+    L.replay_append_host.argtypes = [C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p]
+    return L
 
 
 def shim():
-    """csrc/pve_replay.h compiled by g++ (tests/replay_host), built on demand like the emulator library."""
-    global _shim
-    if _shim is None:
-        subprocess.check_call(["make", "-C", SHIM_DIR, "-s", "libreplay_host.so"])
-        L = C.CDLL(os.path.join(SHIM_DIR, "libreplay_host.so"))
-        L.replay_half_bits_host.argtypes = [C.c_uint32]
-        L.replay_perm_host.restype = None
-        L.replay_perm_host.argtypes = [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_longlong, C.c_void_p]
-        L.replay_append_host.restype = C.c_longlong
-        L.replay_append_host.argtypes = [C.c_longlong, C.c_int, C.c_longlong, C.c_longlong, C.c_longlong, C.c_void_p]
-        _shim = L
-    return _shim
+    """csrc/pve_replay.h compiled by g++ (tests/replay_host), built and loaded by tests/native.py."""
+    return native.load("replay_host", "libreplay_host.so", _signatures)
 
 
 # ------------------------------------------------------------------ 1. the store against the live reference
