@@ -336,6 +336,10 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     typedef typename rollout_args<ACT>::type RArgs;      // (ACT: RolloutArgs + the exploration noise)
     static_assert(!PERS || !PROF, "the persistent form has no phase-cycle diagnostics variant");
     static_assert(!(ACT && IDT), "one action source per variant");
+    // NODRAIN: no global load is pending when a tick issues its first output store, so the wave executes no vmcnt wait from
+    // there until the next tick consumes its own prefetches.  Not the ACT / TRAIN variants, which read rows back
+    // from global memory within the tick.
+    constexpr bool NODRAIN = !ACT && !TRAIN;
     KernargPtr ka0_ = (KernargPtr)__builtin_amdgcn_kernarg_segment_ptr();
     constexpr size_t OFF_P = (sizeof(Const) + 7) / 8 * 8, OFF_R = OFF_P + (sizeof(Params) + 7) / 8 * 8;
     // (WPE = 5, the 96-VGPR experiment: the block without the lane << 16 | j words is 16 368 B -> 10 workgroups per CU)
@@ -344,6 +348,8 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     //  24.78 us -- 9 and 10 resident workgroups per CU run at the same rate, the words buy nothing there)
     typedef Shared<CAP, (CAP == 128 && WPE == 4), (WPE == 5)> ShT;
     __shared__ ShT sh;
+    constexpr bool PARK = NODRAIN && ShT::HOME;
+    static_assert(!PARK || 2 * CAP + 2 * NL <= ShT::POOL, "PARK: 2 NL doubles behind the staged jerks in u_vd");
     __shared__ __attribute__((aligned(64))) float aprm[ACT ? PV_TOTAL : 1];
     __shared__ slot_t<CAP> adsts[ACT ? CAP : 1];     // post-compaction slot of every dense thread's vehicle (SLOT_NONE: gone)
     __shared__ int q_word[4];                       // PERS: item (env, chunk) of the workgroup + the dequeue state of lane 0
@@ -430,6 +436,16 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             r.act = r.alive ? table_action(R.pool, pool_idx, R.table_ids, r.id) : 0.0;
         }
         T::ph_home_store(t0_, sh, r);                   // (HOME: the carried fields to their LDS homes; ordered by the loop's first barrier)
+        // NODRAIN: everything LOAD has requested is consumed in front of the loop.  A register of a load that may still be pending
+        // at the loop's head gets its `s_waitcnt vmcnt` INSIDE the loop, where from the second tick on it waits for nothing but
+        // the previous tick's output stores (one counter for loads and stores, in issue order)
+        if constexpr (NODRAIN) {
+            PVE_PIN(r.alive); PVE_PIN(r.meta); PVE_PIN(r.step); PVE_PIN(r.act);
+            if constexpr (!ShT::HOME) {
+                PVE_PIN(r.p); PVE_PIN(r.v); PVE_PIN(r.a); PVE_PIN(r.jerk_sum); PVE_PIN(r.vir_dis); PVE_PIN(r.closer_p);
+                PVE_PIN(r.id); PVE_PIN(r.seq); PVE_PIN(r.vnum); PVE_PIN(r.count);
+            }
+        }
     }
     double sp_act = 0;                                  // IDT: the action of the vehicle this lane spawns
     for (int k = 0; k < n_ticks; k++) {
@@ -546,6 +562,20 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
         T::ph_keep_prefix(t, sh);
         lds_barrier();                                // (also what orders the previous tick's output stores before this tick's)
         PVE_PHASE_MARK(8)
+        // NODRAIN: the tick's prefetches are consumed HERE, in every lane (0 / +inf where nothing was loaded), in front of FIN's
+        // first output store: they were requested two barriers and the dead-lock scan ago, behind stores a whole tick old.  A
+        // load still pending behind a store makes its consumer wait for the store's acknowledgement too.
+        // PARK (HOME: no register to spare across the observation rows): the values wait in LDS instead -- the action in the
+        // slot's own act_next[] cell (ph_lock2 has read the jerk it may have held), the spawn's action and the arrival time in
+        // u_vd[2 CAP ..), which nothing uses between WALK and the next tick's BUILD
+        if constexpr (NODRAIN) {
+            PVE_PIN(r.next_arr); PVE_PIN(r.act_nx);
+            if constexpr (IDT) PVE_PIN(sp_act);
+            if constexpr (PARK) {
+                if constexpr (IDT) sh.act_next[t] = r.act_nx;
+                if (t < NL) { sh.u_vd[2 * CAP + t] = r.next_arr; if constexpr (IDT) sh.u_vd[2 * CAP + NL + t] = sp_act; }
+            }
+        }
         if constexpr (!ACT && !IDT) { if (!(ShT::HOME && last_tick)) T::ph_park_action(t, sh, r); }   // (HOME, last tick: the cells hold the jerks)
         const Outputs O = T::template tick_outputs<TRAIN>(P, R, k_base_ + k);
         if constexpr (ACT) {
@@ -554,10 +584,19 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
             adsts[t] = (slot_t<CAP>)(adst < 0 ? SLOT_NONE<CAP> : adst);  // (dense thread t; threads >= n_ctl: SLOT_NONE)
         } else T::template ph_final<true, !TRAIN>(c, P, O, env, t, sh, r, fc, k + 1 == n_ticks || (TRAIN && O.state_pre != nullptr));
         PVE_PHASE_MARK(9)
+        double act_mv = 0;                            // PARK + IDT: the parked action on its way to the vehicle's new slot
         if constexpr (IDT) {
-            if (fc.new_slot >= 0) sh.act_next[fc.new_slot] = r.act_nx;   // (act_next = xy32: dead since REWARD)
-            // (a full intersection: who spawns is known since FIN only; the gather is in flight under barrier A and STAGE)
-            if (sp_late) sp_act = (fc.sp_slot >= 0 && nx >= 0) ? table_action(R.pool, nx, R.table_ids, fc.sp_id) : 0.0;
+            // (PARK: a still tick leaves the action where S1 looks for it; else it follows the vehicle like the homes do)
+            if constexpr (PARK) { if (!fc.still) act_mv = sh.act_next[t]; }
+            else if (fc.new_slot >= 0) sh.act_next[fc.new_slot] = r.act_nx;   // (act_next = xy32: dead since REWARD)
+            // (a full intersection: who spawns is known since FIN only)
+            if (sp_late) {
+                sp_act = (fc.sp_slot >= 0 && nx >= 0) ? table_action(R.pool, nx, R.table_ids, fc.sp_id) : 0.0;
+                // (NODRAIN: waited for inside the rare branch -- merged with the common path, STAGE's use of sp_act would carry the
+                //  wait, and with it a drain of FIN's stores, into every staged tick)
+                if constexpr (NODRAIN) PVE_PIN(sp_act);
+                if constexpr (PARK) { if (t < NL) sh.u_vd[2 * CAP + NL + t] = sp_act; }
+            }
         }
         HomeRegs hr;
         T::ph_home_take(t, sh, r, fc, hr);                 // (HOME; the last reads of the old arrangement)
@@ -577,8 +616,10 @@ __global__ __launch_bounds__(CAP) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                     } else T::template ph_state<PERS>(P, O, env, t, sh, r);   // (256 slots: per thread, cf. k_tick)
                 }
             }
+            if constexpr (PARK) { if (fc.sp_slot >= 0) { r.next_arr = sh.u_vd[2 * CAP + t]; if constexpr (IDT) sp_act = sh.u_vd[2 * CAP + NL + t]; } }
             T::ph_stage(c, t, sh, r, fc);
             T::ph_home_put(t, sh, fc, hr);
+            if constexpr (PARK && IDT) { if (fc.new_slot >= 0) sh.act_next[fc.new_slot] = act_mv; }
             if constexpr (IDT) { if (fc.sp_slot >= 0) sh.act_next[fc.sp_slot] = sp_act; }
             if constexpr (ACT) {
                 // next tick's actions: the vehicle lane t spawns gets the action of an all-zero row (ref :380, :420), the
