@@ -444,6 +444,29 @@ int pve_learner_init(pve_handle h, const pve_learner *lrn, const float *actor, c
 int pve_learner_step(pve_handle h, const pve_learner *lrn, const float *rows, const float *act7, const float *target,
                      int64_t batch, int64_t n_batches, float *losses /* or NULL */, float *grads /* or NULL */);
 
+/* THE WIDE LEARNER STEP: the same step (main.py:48-84) on batches larger than the reference's 128, spread over the chip.
+ * Additive within ABI 9: one new symbol, PVE_ABI_VERSION stays 9.  A batch of `batch` rows is ceil(batch / PVE_LEARN_SLICE)
+ * slices of 128 rows (the last may be shorter).  Every slice is worked like a batch of pve_learner_step, its sums starting from 0
+ * at its first row, with dQ scaled by the WHOLE batch; the gradient of a parameter, and each loss sum, is then partial[0] +
+ * partial[1] + ... in ascending slice order, plain float32 adds, and Adam and the soft update follow unchanged
+ * (csrc/pve_learn.h, learn_steps_wide: the definition, which a host compiler builds as well).  For batch <= 128 the result is
+ * pve_learner_step's bit for bit; for larger batches it is another, equally fixed order of summation: it depends on `batch`
+ * alone, not on `groups`, block_threads or the device.
+ * Per minibatch four launches on the handle's stream (slice pass and apply for the critic, then for the actor with the updated
+ * critic; two with PVE_LEARN_CRITIC_ONLY), no host synchronisation; n_batches steps are enqueued in order.
+ * work: caller-owned DEVICE scratch of work_floats >= PVE_LEARNER_WIDE_FLOATS(batch) float32, 16-byte aligned: one row of
+ * PVE_LEARNER_WIDE_ROW floats per slice (critic gradients padded to 6844, actor gradients padded to 6396, the two loss sums + 2
+ * reserved).  It needs no initialisation: whatever is read was written by the same call.  It must not be shared by calls on
+ * different streams.  groups: workgroups of the slice passes; 0 = one per slice, at most one per compute unit.
+ * Everything else, and every error, as pve_learner_step; in addition PVE_ERR_INVALID for a null or misaligned work, a work_floats
+ * too small and groups < 0. */
+#define PVE_LEARN_SLICE 128
+#define PVE_LEARNER_WIDE_ROW 13244
+#define PVE_LEARNER_WIDE_FLOATS(batch) ((((batch) + 127) / 128) * PVE_LEARNER_WIDE_ROW)
+int pve_learner_step_wide(pve_handle h, const pve_learner *lrn, const float *rows, const float *act7, const float *target,
+                          int64_t batch, int64_t n_batches, float *work, int64_t work_floats, int32_t groups,
+                          float *losses /* or NULL */, float *grads /* or NULL */);
+
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly
  * pve_step_all() with

@@ -25,6 +25,7 @@ PVE_ACTOR_N_WEIGHTS = 6393
 PVE_CRITIC_N_WEIGHTS = 6841
 NSTEP_TAIL, NSTEP_MAX_WINDOW, NSTEP_RECORD = 0x1, 16, 36
 REPLAY_STATE_WORDS = 4
+LEARN_SLICE, LEARNER_WIDE_ROW = 128, 13244
 ABI_VERSION = 9
 SRC_ZERO, SRC_POOL, SRC_ACTOR, SRC_TABLE = 0, 1, 2, 3
 
@@ -103,7 +104,8 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_step_all_actor", "pve_debug_traffic_probe", "pve_set_intentions", "pve_step_many", "pve_set_actor",
            "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise",
            "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather",
-           "pve_replay_reset", "pve_replay_append", "pve_replay_sample", "pve_learner_init", "pve_learner_step")
+           "pve_replay_reset", "pve_replay_append", "pve_replay_sample", "pve_learner_init", "pve_learner_step",
+           "pve_learner_step_wide")
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -146,6 +148,7 @@ def _declare(L):
     L.pve_replay_sample.argtypes = [vp, C.POINTER(PveReplay), C.c_int64, C.c_int64, vp, vp, vp, vp]
     L.pve_learner_init.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, vp]
     L.pve_learner_step.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
+    L.pve_learner_step_wide.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
     for name in EXPORTS:

@@ -52,6 +52,8 @@
 //                                      const float *target_critic, float beta1, float beta2, void *stream, std::string &err);
 //     static int   launch_learner_step(const pve::LearnCtx &, int block_threads, void *stream, std::string &err);
 //                                                // optional, both or none: pve_learner_init / pve_learner_step (csrc/pve_learn.h)
+//     static int   launch_learner_step_wide(const pve::LearnCtx &, float *work, int groups, int block_threads, void *stream,
+//                                           std::string &err);     // optional: pve_learner_step_wide (learn_steps_wide)
 //   };
 //
 // pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
@@ -273,6 +275,21 @@ template <class B> struct backend_learner<B, decltype((void)&B::launch_learner_s
                     std::string &err) { return B::launch_learner_init(P, a, c, ta, tc, beta1, beta2, stream, err); }
     static int step(const LearnCtx &C, int block, void *stream, std::string &err) { return B::launch_learner_step(C, block, stream, err); }
 };
+// The wide step (pve_learner_step_wide) likewise, behind Backend::launch_learner_step_wide.
+template <class B, class = void> struct backend_learner_wide {
+    static constexpr bool value = false;
+    static int step(const LearnCtx &, float *, int, int, void *, std::string &) { return -1; }
+};
+template <class B> struct backend_learner_wide<B, decltype((void)&B::launch_learner_step_wide)> {
+    static constexpr bool value = true;
+    static int step(const LearnCtx &C, float *work, int groups, int block, void *stream, std::string &err)
+    {
+        return B::launch_learner_step_wide(C, work, groups, block, stream, err);
+    }
+};
+static_assert(LEARN_SLICE == PVE_LEARN_SLICE && LW_ROW == PVE_LEARNER_WIDE_ROW && LW_ROW % 4 == 0 &&
+              PVE_LEARNER_WIDE_FLOATS(1) == LW_ROW && PVE_LEARNER_WIDE_FLOATS(128) == LW_ROW && PVE_LEARNER_WIDE_FLOATS(129) == 2 * LW_ROW,
+              "the wide step's workspace (include/pve_env.h PVE_LEARNER_WIDE_*)");
 static_assert(LB_ACTOR == PVE_LEARNER_ACTOR && LB_CRITIC == PVE_LEARNER_CRITIC && LB_TACTOR == PVE_LEARNER_TARGET_ACTOR &&
               LB_TCRITIC == PVE_LEARNER_TARGET_CRITIC && LB_M_ACTOR == PVE_LEARNER_M_ACTOR && LB_V_ACTOR == PVE_LEARNER_V_ACTOR &&
               LB_M_CRITIC == PVE_LEARNER_M_CRITIC && LB_V_CRITIC == PVE_LEARNER_V_CRITIC && LB_POWERS == PVE_LEARNER_POWERS &&
@@ -767,6 +784,34 @@ int pve_learner_step(pve_handle h, const pve_learner *lrn, const float *rows, co
     DevScope dev_scope(h->device);
     std::string err;
     if (backend_learner<Backend>::step(C, lrn->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_learner_step: " + err);
+    return PVE_OK;
+}
+
+int pve_learner_step_wide(pve_handle h, const pve_learner *lrn, const float *rows, const float *act7, const float *target, int64_t batch,
+                          int64_t n_batches, float *work, int64_t work_floats, int32_t groups, float *losses, float *grads)
+{
+    LearnCtx C;
+    memset(&C, 0, sizeof(C));
+    const int rc = learner_args(h, lrn, "pve_learner_step_wide", C.H);
+    if (rc != PVE_OK) return rc;
+    if (!rows || !act7 || !target) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: null rows, act7 or target");
+    if (batch < 1) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: batch must be >= 1");
+    if (n_batches < 1 || n_batches > 0x7fffffffLL / batch)
+        return fail(PVE_ERR_INVALID, "pve_learner_step_wide: n_batches must be >= 1 and batch * n_batches <= 2^31 - 1");
+    if (((uintptr_t)rows & 15) || (((uintptr_t)act7 | (uintptr_t)target | (uintptr_t)losses | (uintptr_t)grads) & 3))
+        return fail(PVE_ERR_INVALID, "pve_learner_step_wide: rows must be 16-byte aligned, act7, target, losses and grads 4-byte aligned");
+    if (!work) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: null work");
+    if ((uintptr_t)work & 15) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: work must be 16-byte aligned");
+    if (work_floats < (int64_t)PVE_LEARNER_WIDE_FLOATS(batch))
+        return fail(PVE_ERR_INVALID, "pve_learner_step_wide: work_floats must be >= PVE_LEARNER_WIDE_FLOATS(batch)");
+    if (groups < 0) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: groups must be >= 0");
+    if (!backend_learner_wide<Backend>::value) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: this backend has no learner kernels");
+    C.P = lrn->params; C.rows = rows; C.act7 = act7; C.target = target; C.losses = losses; C.grads = grads;
+    C.batch = (int)batch; C.n_batches = (int)n_batches;
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_learner_wide<Backend>::step(C, work, (int)groups, lrn->block_threads, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_learner_step_wide: " + err);
     return PVE_OK;
 }
 

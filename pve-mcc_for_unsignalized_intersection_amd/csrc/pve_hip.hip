@@ -1055,6 +1055,25 @@ __global__ __launch_bounds__(1024) void k_learner_step(LearnCtx C)
     learn_steps(LearnWg{(int)threadIdx.x, (int)blockDim.x}, C);
 }
 
+// The wide step (learn_steps_wide): per minibatch k_learner_slice<critic>, k_learner_apply<critic>, k_learner_slice<actor>,
+// k_learner_apply<actor> on one stream; what one launch writes the next reads behind the kernel boundary, nothing else orders them.
+// k_learner_slice: workgroup g of G runs learn_slice on slices g, g + G, ... as LearnWg does above (same LDS, same barriers) and
+// leaves each slice's row of the workspace complete.  No workgroup reads what another writes.
+template <bool CRITIC> __global__ __launch_bounds__(1024) void k_learner_slice(LearnCtx C, float *work, int step, int n_slices)
+{
+    extern __shared__ __attribute__((aligned(16))) float learn_s[];
+    C.tape = learn_s; C.S = learn_s + LEARN_TAPE;
+    const LearnWg E{(int)threadIdx.x, (int)blockDim.x};
+    for (int s = blockIdx.x; s < n_slices; s += gridDim.x) learn_slice(E, C, step, s, CRITIC, work + (size_t)s * LW_ROW);
+}
+// k_learner_apply: ONE workgroup adds the rows in ascending slice order (item i to thread i mod blockDim.x, which also applies it),
+// then Adam, the soft update, the powers and, behind the step's last pass, the count, the losses and the `grads` row.
+template <bool CRITIC> __global__ __launch_bounds__(1024) void k_learner_apply(LearnCtx C, const float *__restrict__ work, int step, int n_slices)
+{
+    if (blockIdx.x != 0) return;
+    learn_combine(LearnWg{(int)threadIdx.x, (int)blockDim.x}, C, step, CRITIC, work, n_slices);
+}
+
 // pve_learner_init: the four networks into the block, moments / count / gradients zeroed, the powers set to beta1, beta2
 __global__ __launch_bounds__(256) void k_learner_init(float *__restrict__ P, const float *__restrict__ actor, const float *__restrict__ critic,
                                                       const float *__restrict__ tactor, const float *__restrict__ tcritic, float beta1, float beta2)
@@ -1540,6 +1559,44 @@ struct Backend {
         const int block = block_threads > 0 ? block_threads : 1024;
         hipLaunchKernelGGL(k_learner_step, dim3(1), dim3(block), lds, (hipStream_t)stream, C);
         return check_launch(err);
+    }
+    // pve_learner_step_wide: four launches per minibatch (two with PVE_LEARN_CRITIC_ONLY), enqueued in order, no host
+    // synchronisation.  groups = 0: one workgroup per slice, at most one per CU.  The slice kernels take the same dynamic LDS as
+    // k_learner_step: the function attribute once per kernel and device.
+    static int launch_learner_step_wide(const LearnCtx &C, float *work, int groups, int block_threads, void *stream, std::string &err)
+    {
+        constexpr size_t lds = sizeof(float) * LEARN_LDS_FLOATS;
+        static std::mutex mu;
+        static int n_cu[64] = {};
+        int dev = 0, cus = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) { err = hip_err("hipGetDevice", e); return -1; }
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            if (dev < 0 || dev >= 64 || !n_cu[dev]) {
+                e = hipFuncSetAttribute((const void *)k_learner_slice<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e == hipSuccess)
+                    e = hipFuncSetAttribute((const void *)k_learner_slice<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (e != hipSuccess) { err = hip_err("hipFuncSetAttribute", e); return -1; }
+                e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+                if (e != hipSuccess || cus <= 0) { err = hip_err("hipDeviceGetAttribute", e); return -1; }
+                if (dev >= 0 && dev < 64) n_cu[dev] = cus;
+            } else cus = n_cu[dev];
+        }
+        const int n_slices = learn_n_slices(C.batch), want = groups > 0 ? groups : cus;
+        const int grid = n_slices < want ? n_slices : want, block = block_threads > 0 ? block_threads : 1024;
+        const bool with_actor = !(C.H.flags & LEARN_CRITIC_ONLY);
+        hipStream_t s = (hipStream_t)stream;
+        for (int step = 0; step < C.n_batches; step++) {
+            hipLaunchKernelGGL(k_learner_slice<true>, dim3(grid), dim3(block), lds, s, C, work, step, n_slices);
+            hipLaunchKernelGGL(k_learner_apply<true>, dim3(1), dim3(block), 0, s, C, (const float *)work, step, n_slices);
+            if (with_actor) {
+                hipLaunchKernelGGL(k_learner_slice<false>, dim3(grid), dim3(block), lds, s, C, work, step, n_slices);
+                hipLaunchKernelGGL(k_learner_apply<false>, dim3(1), dim3(block), 0, s, C, (const float *)work, step, n_slices);
+            }
+            if (check_launch(err) != 0) return -1;
+        }
+        return 0;
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)
     {

@@ -21,6 +21,12 @@
 //                       dx[k] = rstd * ((dxh[k] - m1) - xh[k] * m2)
 //   every gradient of a parameter is acc = 0; b = 0 .. batch-1 ascending: acc = fmaf(A[b], B[b], acc) with the pair (A, B) of
 //   learn_grad_src (A = 1 for biases and betas); the losses sum over b in the same way.
+//   THE WIDE STEP (learn_steps_wide; pve_learner_step_wide) cuts a batch of B rows into ceil(B / 128) slices, slice s = rows
+//   128 s .. min(B, 128 s + 128) - 1 (LEARN_SLICE).  Within a slice every chain above starts from 0 at the slice's first row and
+//   runs as in learn_steps; dQ stays 2 (Q - target) / (float)B and -1 / (float)B with the whole batch B.  Then, per parameter and
+//   for each of the two loss sums: acc = partial[0]; s = 1 .. n_slices - 1 ascending: acc = acc + partial[s], plain float32 adds;
+//   the loss sums are divided by (float)B behind that.  For B <= 128 this IS learn_steps, bit for bit; for B > 128 it is another
+//   order, as fixed as the first: it depends on B alone, not on the grid, the threads or the sub-block sizes.
 //
 // ADAM as tf.train.AdamOptimizer applies it (TF 1.x ApplyAdam, written from memory of TensorFlow -- this header is the project's
 // definition): alpha = lr * sqrtf(1 - b2p) / (1 - b1p);  m += (g - m) * (1 - beta1);  v += (g * g - v) * (1 - beta2);
@@ -387,6 +393,136 @@ template <class Exec> PVE_HD void learn_steps(const Exec &E, const LearnCtx C)
                 }
             } else gout[LRN_CRITIC_W + i - 1] = 0.f;                            // critic only: no actor gradient was applied
         });
+    }
+}
+
+// =================================================================== the WIDE step: a batch in slices of PVE_LEARN_SLICE rows
+// (see ORDERS).  A slice pass leaves its slice's partial gradients and partial loss sum in that slice's row of a caller-owned
+// workspace; a combine phase adds the rows in ascending order into LB_GRAD and applies learn_adam.  Slice passes of different slices
+// share nothing but the weights they read, so the device gives each to a workgroup of its own (pve_hip.hip k_learner_slice /
+// k_learner_apply); learn_steps_wide under LearnSeq is the host definition.
+constexpr int LEARN_SLICE = 128;                                  // PVE_LEARN_SLICE
+// one slice's row of the workspace: critic gradients (padded), actor gradients (padded), then critic / actor loss sum + 2 reserved
+constexpr int LW_CRITIC = 0, LW_ACTOR = LW_CRITIC + lrn_pad4(LRN_CRITIC_W), LW_LOSS = LW_ACTOR + lrn_pad4(LRN_ACTOR_W),
+              LW_ROW = LW_LOSS + 4;                               // PVE_LEARNER_WIDE_ROW
+PVE_HD int learn_n_slices(int batch) { return (batch + LEARN_SLICE - 1) / LEARN_SLICE; }
+
+// ---- one pass (critic: learn_steps' step 1; else its step 2) over slice s of minibatch `step`, into the slice's row R.  Every
+// chain starts from 0 at the slice's first row and continues across the slice's sub-blocks; dQ is scaled by the WHOLE batch.
+template <class Exec> PVE_HD void learn_slice(const Exec &E, const LearnCtx C, int step, int s, bool critic, float *R)
+{
+    const LearnNet NA = learn_net(false), NC = learn_net(true);
+    const int B = C.batch, r0 = s * LEARN_SLICE, ns = B - r0 < LEARN_SLICE ? B - r0 : LEARN_SLICE;
+    float *const P = C.P, *const T = C.tape;
+    const float *const Wa = P + LB_ACTOR, *const Wc = P + LB_CRITIC;
+    const size_t first_row = (size_t)step * B + r0;
+    const float *rows = C.rows + first_row * LRN_IN, *act7 = C.act7 + first_row * LRN_ACT, *target = C.target + first_row;
+    if (critic) {
+        float *const G = R + LW_CRITIC, *const L = R + LW_LOSS;
+        for (int b0 = 0; b0 < ns; b0 += LEARN_SUB_1) {
+            const int n = ns - b0 < LEARN_SUB_1 ? ns - b0 : LEARN_SUB_1, ts = LEARN_STRIDE_1;
+            E.forall(n * 8, [=](int i) {
+                const int b = i / 8, e = i % 8;
+                if (e < LRN_ACT) T[b * ts + T_ACT + e] = act7[(size_t)(b0 + b) * LRN_ACT + e];
+                else T[b * ts + T_TGT] = target[b0 + b];
+            });
+            learn_forward(E, NC, Wc, T, ts, rows + (size_t)b0 * LRN_IN, n);
+            E.forall(n, [=](int b) {
+                float *t = T + b * ts;
+                t[T_DOUT] = 2.0f * (t[T_OUT] - t[T_TGT]) / (float)B;
+            });
+            E.forall(1, [=](int) {
+                float acc = b0 ? L[S_LOSS_C] : 0.f;
+                for (int b = 0; b < n; b++) { const float d = T[b * ts + T_TGT] - T[b * ts + T_OUT]; acc = fmaf(d, d, acc); }
+                L[S_LOSS_C] = acc;
+            });
+            learn_backward(E, NC, Wc, T, ts, n, true);
+            learn_accumulate(E, NC, G, T, ts, n, b0 == 0);
+        }
+    } else {
+        float *const G = R + LW_ACTOR, *const L = R + LW_LOSS;
+        for (int b0 = 0; b0 < ns; b0 += LEARN_SUB_2) {
+            const int n = ns - b0 < LEARN_SUB_2 ? ns - b0 : LEARN_SUB_2, ts = LEARN_STRIDE_2;
+            float *Tc = T + T_NET;
+            learn_forward(E, NA, Wa, T, ts, rows + (size_t)b0 * LRN_IN, n);
+            E.forall(n * 8, [=](int i) {
+                const int b = i / 8, e = i % 8;
+                if (e == 0) { const float a = learn_tanh3(T[b * ts + T_OUT]); T[b * ts + T_OUT] = a; Tc[b * ts + T_ACT] = a; }
+                else if (e < LRN_ACT) Tc[b * ts + T_ACT + e] = act7[(size_t)(b0 + b) * LRN_ACT + e];
+                else Tc[b * ts + T_DOUT] = -1.0f / (float)B;
+            });
+            learn_forward(E, NC, Wc, Tc, ts, rows + (size_t)b0 * LRN_IN, n);
+            E.forall(1, [=](int) {
+                float acc = b0 ? L[S_LOSS_A] : 0.f;
+                for (int b = 0; b < n; b++) acc += Tc[b * ts + T_OUT];
+                L[S_LOSS_A] = acc;
+            });
+            learn_backward(E, NC, Wc, Tc, ts, n, false);
+            E.forall(n, [=](int b) { T[b * ts + T_DOUT] = Tc[b * ts + T_M1] * learn_dtanh3(T[b * ts + T_OUT]); });
+            learn_backward(E, NA, Wa, T, ts, n, true);
+            learn_accumulate(E, NA, G, T, ts, n, b0 == 0);
+        }
+    }
+}
+
+// ---- the combine phase of one network: the slices' rows added in ascending order into LB_GRAD, learn_adam on the sum; behind the
+// last pass of a step (`last`: the actor's, or the critic's with LEARN_CRITIC_ONLY) the step count and what learn_steps reports
+template <class Exec> PVE_HD void learn_combine(const Exec &E, const LearnCtx C, int step, bool critic, const float *work, int n_slices)
+{
+    const LearnNet N = learn_net(critic);
+    const int B = C.batch, off = critic ? LW_CRITIC : LW_ACTOR;
+    float *const P = C.P, *const G = P + LB_GRAD + (critic ? 0 : lrn_pad4(LRN_CRITIC_W));
+    float *gout = C.grads ? C.grads + (size_t)step * LRN_GRADS : nullptr;
+    E.forall(N.total, [=](int i) {
+        const float *p = work + off + i;
+        float acc = p[0];
+        int s = 1;
+        for (; s + 8 <= n_slices; s += 8) {                                     // eight loads in flight; the adds in their one order
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) v[j] = p[(size_t)(s + j) * LW_ROW];
+#pragma unroll
+            for (int j = 0; j < 8; j++) acc = acc + v[j];
+        }
+        for (; s < n_slices; s++) acc = acc + p[(size_t)s * LW_ROW];
+        G[i] = acc;
+    });
+    if (critic) learn_adam(E, N, C.H, C.H.critic_lr, P, LB_CRITIC, LB_TCRITIC, LB_M_CRITIC, LB_V_CRITIC, LB_POWERS + 2, G, gout);
+    else learn_adam(E, N, C.H, C.H.actor_lr, P, LB_ACTOR, LB_TACTOR, LB_M_ACTOR, LB_V_ACTOR, LB_POWERS, G, gout ? gout + LRN_CRITIC_W : nullptr);
+    const bool with_actor = !(C.H.flags & LEARN_CRITIC_ONLY), last = !critic || !with_actor;
+    float *losses = C.losses;
+    E.forall(last && !with_actor && gout ? 1 + LRN_ACTOR_W : 1, [=](int i) {
+        if (i == 0) {
+            if (last) {
+                int32_t cnt;
+                memcpy(&cnt, P + LB_STEPS, 4);
+                cnt++;
+                memcpy(P + LB_STEPS, &cnt, 4);
+            }
+            if (losses) {
+                const int k = critic ? S_LOSS_C : S_LOSS_A;
+                float acc = work[LW_LOSS + k];
+                for (int s = 1; s < n_slices; s++) acc = acc + work[(size_t)s * LW_ROW + LW_LOSS + k];
+                if (critic) {
+                    losses[2 * step] = acc / (float)B;
+                    if (!with_actor) losses[2 * step + 1] = 0.f;
+                } else losses[2 * step + 1] = -(acc / (float)B);
+            }
+        } else gout[LRN_CRITIC_W + i - 1] = 0.f;                                // critic only: no actor gradient was applied
+    });
+}
+
+// ---- n_batches wide steps in sequence (work: learn_n_slices(batch) * LW_ROW floats; no float of it is read before it is written)
+template <class Exec> PVE_HD void learn_steps_wide(const Exec &E, const LearnCtx C, float *work)
+{
+    const int n_slices = learn_n_slices(C.batch);
+    const bool with_actor = !(C.H.flags & LEARN_CRITIC_ONLY);
+    for (int step = 0; step < C.n_batches; step++) {
+        for (int s = 0; s < n_slices; s++) learn_slice(E, C, step, s, true, work + (size_t)s * LW_ROW);
+        learn_combine(E, C, step, true, work, n_slices);
+        if (!with_actor) continue;
+        for (int s = 0; s < n_slices; s++) learn_slice(E, C, step, s, false, work + (size_t)s * LW_ROW);
+        learn_combine(E, C, step, false, work, n_slices);
     }
 }
 

@@ -30,6 +30,12 @@ M_ACTOR, V_ACTOR, M_CRITIC, V_CRITIC = 26480, 32876, 39272, 46116
 POWERS, STEPS, GRAD, N_FLOATS = 52960, 52964, 52968, 66208
 GRAD_ACTOR = GRAD + 6844
 CRITIC_ONLY = 0x1
+SLICE, WIDE_ROW = _capi.LEARN_SLICE, _capi.LEARNER_WIDE_ROW         # step_wide: rows per slice, workspace floats per slice
+
+
+def wide_floats(batch):
+    """PVE_LEARNER_WIDE_FLOATS(batch): the float32 workspace pve_learner_step_wide needs for a batch"""
+    return (int(batch) + SLICE - 1) // SLICE * WIDE_ROW
 
 
 def _shapes(critic):
@@ -271,6 +277,48 @@ class Learner:
             self._lr.flags = CRITIC_ONLY if critic_only else 0
             self._call(b.lib.pve_learner_step, "pve_learner_step", C.c_void_p(rows.data_ptr()), C.c_void_p(act7.data_ptr()),
                        C.c_void_p(target.data_ptr()), B, n, *[C.c_void_p(o.data_ptr() if o is not None else 0) for o in outs])
+        return outs[0], outs[1]
+
+    def step_wide(self, rows, act7, target, losses=None, grads=None, critic_only=False, groups=0):
+        """`step` for large batches (pve_learner_step_wide): the batch is cut into slices of 128 rows, the slices are worked by
+        one workgroup each across the chip and their gradients added in ascending slice order (csrc/pve_learn.h,
+        learn_steps_wide).  Same arguments and return value as `step`; up to 128 rows the same bits as `step`, beyond that a
+        different, equally fixed order of summation that depends on the batch size alone.  groups: workgroups of the slice
+        passes, 0 = one per slice up to the device's compute units (no result depends on it).  The workspace is allocated on the
+        batch's stream, kept, and grown with the batch.  Never synchronises."""
+        torch = self._torch
+        b = self.batch
+        with b._own_stream():
+            for x, what in ((rows, "rows"), (act7, "act7"), (target, "target")):
+                if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device != self.params.device:
+                    raise PveError("Learner.step_wide: %s must be a float32 tensor on %s" % (what, self.params.device))
+            if rows.dim() == 2:
+                rows, act7, target = rows[None], act7[None], target[None]
+            if rows.dim() != 3 or rows.shape[2] != 28 or rows.shape[1] < 1 or rows.shape[0] < 1 or \
+                    tuple(act7.shape) != tuple(rows.shape[:2]) + (7,) or tuple(target.shape) != tuple(rows.shape[:2]):
+                raise PveError("Learner.step_wide: rows [n_batches, batch, 28], act7 [.., 7] and target [..] are needed")
+            n, B = int(rows.shape[0]), int(rows.shape[1])
+            rows, act7, target = rows.contiguous(), act7.contiguous(), target.contiguous()
+            outs = []
+            for o, width, what in ((losses, 2, "losses"), (grads, N_GRADS, "grads")):
+                if o is None or o is False:
+                    outs.append(None)
+                elif o is True:
+                    outs.append(torch.empty(n, width, dtype=torch.float32, device=self.params.device))
+                else:
+                    if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.numel() != n * width or \
+                            o.device != self.params.device:
+                        raise PveError("Learner.step_wide: %s must be a contiguous float32 device tensor [%d, %d]" % (what, n, width))
+                    outs.append(o)
+            need = wide_floats(B)
+            work = getattr(self, "_wide_work", None)
+            if work is None or work.numel() < need:
+                # (never zeroed: every float a launch reads was written by an earlier launch of the same call)
+                work = self._wide_work = torch.empty(need, dtype=torch.float32, device=self.params.device)
+            self._lr.flags = CRITIC_ONLY if critic_only else 0
+            self._call(b.lib.pve_learner_step_wide, "pve_learner_step_wide", C.c_void_p(rows.data_ptr()), C.c_void_p(act7.data_ptr()),
+                       C.c_void_p(target.data_ptr()), B, n, C.c_void_p(work.data_ptr()), work.numel(), int(groups),
+                       *[C.c_void_p(o.data_ptr() if o is not None else 0) for o in outs])
         return outs[0], outs[1]
 
     # ---- views of the block, in the layouts set_actor / set_target_networks take
