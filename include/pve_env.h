@@ -199,6 +199,18 @@ int pve_compact(pve_handle h, double *obs_post /* optional: rows are moved with 
  * layouts, checkpoint names `agent1actor/...`); they are copied into the handle's workspace (flat, and packed for the
  * matrix cores: centered over the output units, split into half pairs, in operand order), so the caller's buffer may be
  * reused afterwards; call it again after every update of the weights.
+ * Range of the split-half form.  A half pair hi + lo holds 22 significant bits only while lo is a normal f16 number, i.e. for
+ * values in [2^-3, 2^15).  The WEIGHTS are brought there at pack time: each centred dense kernel (and its centred bias) is
+ * multiplied by 2^e, e = 0 while its largest entry M is in [2^-3, 2^12], else e = -floor(log2 M) clamped to +-40, and the
+ * LayerNorm behind it runs with the variance epsilon 1e-12f * 4^e: exact in float32, and the same function of the weights at
+ * every scale a training run passes through (a freshly initialised network, kernels ~ 3e-3, included; e = 0 changes no bit).
+ * The ACTIVATIONS are split as they are.  Documented limits: (1) a LayerNorm output must stay below f16's largest number,
+ * |gamma| * sqrt(63) + |beta| < 65 504 for LayerNorm_1 and LayerNorm_2 (sqrt(27) for the input LayerNorm); beyond, hi is inf
+ * and the action is meaningless.  (2) A row whose input LayerNorm returns values far below 1 -- the all-zero row, or a row
+ * whose spread is far below sqrt(1e-12) = 1e-6, while ln0_beta is near 0 as it is right after initialisation -- is contracted
+ * with fewer than 22 bits (measured on the CPU model: up to 6e-4 on actions of a freshly initialised actor for rows with a
+ * spread of 1e-12; an observation row holds a position, a speed and a route and is nowhere near).  PVE_CFG_ACTOR_F32 has
+ * neither limit.  tests/split_half_model.py is the CPU statement of this arithmetic.
  * pve_actor_forward: obs = [n_envs][cap][28] float64 (= obs_post of the previous tick, zeros after reset);
  * actions: [n_envs][cap] float64 out.  `weights` = NULL uses the installed actor; non-NULL = pve_set_actor(weights) first. */
 #define PVE_ACTOR_N_WEIGHTS 6393
@@ -256,7 +268,9 @@ int pve_set_action_noise(pve_handle h, double sigma, uint64_t seed, int64_t env_
  * on load, as the graph's placeholders do.  n is any positive count, not tied to n_envs * capacity: one tick's state_pre and
  * flags blocks, or a whole [n_ticks][n_envs][cap] trajectory in one call.  Both calls are asynchronous on the handle's stream
  * and need no pve_reset.  The target networks always run in the split-half matrix-core form (three v_mfma_f32_32x32x16_f16
- * per block, float32 accumulation), with or without PVE_CFG_ACTOR_F32.
+ * per block, float32 accumulation), with or without PVE_CFG_ACTOR_F32.  The pack-time scale and the two limits stated at
+ * pve_set_actor hold for both networks; the critic's second dense kernel is scaled as a whole, its seven action rows included
+ * (the actions, |a| <= 3, are activations like the hidden units), and limit (1) reads |gamma| * sqrt(63) + |beta| < 65 504.
  * Errors: null or non-positive arguments PVE_ERR_INVALID; networks not installed PVE_ERR_STATE; a backend without the
  * kernels PVE_ERR_INVALID. */
 #define PVE_CRITIC_N_WEIGHTS 6841

@@ -300,9 +300,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
 // ------------------------------------------------------------------------------------------------------
 // The split-half actor (default): every float32 operand is split into two halves, x = hi + lo (hi = half(x), lo =
-// half(x - hi): 22 significant bits; gfx950's matrix cores honour f16 subnormals -- tools/mfma32_layout_probe.hip), and
-// each product block is three v_mfma_f32_32x32x16_f16 (hi*hi + hi*lo + lo*hi, float32 accumulation; the lo*lo term is
-// 2^-22 relative).  One TILE = 32 vehicles on one wave: lane (j = lane & 31, hf = lane >> 5) holds, for vehicle j,
+// half(x - hi); gfx950's matrix cores honour f16 subnormals -- tools/mfma32_layout_probe.hip), and each product block is
+// three v_mfma_f32_32x32x16_f16 (hi*hi + hi*lo + lo*hi, float32 accumulation; the lo*lo term is 2^-22 relative).
+// What the pair guarantees: hi carries 11 significant bits, lo the next 11 -- 22 in all -- ONLY while lo is a normal f16
+// number, that is for 2^-3 <= |x| < 2^15 (lo is then at least 2^-14).  Below, lo sinks into f16's subnormal range, whose
+// step is 2^-24 whatever |x| is: at |x| = 3e-3, the size of a freshly initialised dense kernel (model_agent_maddpg.py:29),
+// 14 bits are left, and the actions were 50 to 100 times further from float64 than a float32 evaluation is; above 65 504
+// hi is inf.  LayerNorm makes every dense layer scale-invariant, so k_actor_pack multiplies each centred dense kernel and its
+// centred bias by a power of two 2^e that brings the kernel's largest entry into [1, 2) (pack_exponent below: e = 0 while
+// that entry is in [2^-3, 2^12], so the shipped checkpoint keeps its bits) and stores 1e-12f * 4^e as the variance epsilon
+// of the LayerNorm that follows (PV_EPS1 / PV_EPS2): the products are exact multiples, the LayerNorm divides the factor out,
+// and the half pairs hold their 22 bits at every scale a training run passes through.  The ACTIVATIONS (LayerNorm outputs,
+// the critic's actions) are split at run time and have no such scale: they are O(|gamma|) by construction and must stay
+// below 65 504, |gamma| sqrt(63) + |beta| < 65 504 per LayerNorm; only a row whose LayerNorm_0 output is far below 1 -- the
+// all-zero row or a row with a spread far below 1e-6, under a ln0_beta near 0 -- is contracted with fewer bits.
+// tests/split_half_model.py states this arithmetic on the CPU, tests/test_gpu_split_half.py holds the kernels to it.
+// One TILE = 32 vehicles on one wave: lane (j = lane & 31, hf = lane >> 5) holds, for vehicle j,
 //   inputs   x[c], c = 0..15: feature 16 (c >> 3) + 8 hf + (c & 7)  (features 28..31 = zero padding of K to 32)
 //   hidden   acc[m][r], m = 0..1, r = 0..15: unit u(m, r, hf) = 32 m + 8 (r >> 2) + 4 hf + (r & 3)
 // which is at once the C/D layout of one layer and -- with the contraction index enumerated accordingly -- the B-operand
@@ -333,6 +346,7 @@ constexpr int AP_PRM = AP_A2 + 2 * 2 * 4 * 64 * 8 * 2;     // float [PV_TOTAL]
 // float parameter vectors in LANE ORDER: vec[(hf * 2 + m) * 16 + r] = parameter of unit u(m, r, hf)
 constexpr int PV_B1 = 0, PV_G1 = 64, PV_BE1 = 128, PV_B2 = 192, PV_G2 = 256, PV_BE2 = 320, PV_W3 = 384,
               PV_LN0G = 448 /* [hf][c 16] */, PV_LN0B = 480, PV_B3 = 512, PV_A0 = 513 /* action of the all-zero row */,
+              PV_EPS1 = 514, PV_EPS2 = 515 /* variance epsilon of LayerNorm_1 / _2: 1e-12f * 4^e of the layer's pack factor */,
               PV_TOTAL = 516;
 constexpr int AP_BYTES = AP_PRM + PV_TOTAL * 4;
 constexpr int AP_BYTES_PADDED = (AP_BYTES + 255) / 256 * 256;
@@ -394,12 +408,14 @@ __device__ __forceinline__ float actor_hsum16(pve_v16f e)
 
 // LayerNorm (input already centered by the centered dense kernel) + ReLU over the 64 hidden units of a vehicle, 32 of
 // them in this lane; gam / bet point at this lane's 32 parameters (lane order)
-__device__ __forceinline__ void actor_ln_relu32(pve_v16f (&v)[2], const float *gam, const float *bet)
+// eps: the variance epsilon of this layer as k_*_pack stored it, 1e-12f * 4^e for a dense kernel packed with the factor 2^e
+// (PV_EPS1 / PV_EPS2 below; 1e-12f itself for e = 0)
+__device__ __forceinline__ void actor_ln_relu32(pve_v16f (&v)[2], const float *gam, const float *bet, float eps)
 {
     pve_v16f e = v[0] * v[0];
     e = __builtin_elementwise_fma(v[1], v[1], e);
     const float s = actor_hsum16(e);
-    const float rstd = __builtin_amdgcn_rsqf(actor_xsum2(s) * (1.0f / (float)ACT_H) + 1e-12f);
+    const float rstd = __builtin_amdgcn_rsqf(actor_xsum2(s) * (1.0f / (float)ACT_H) + eps);
 #pragma unroll
     for (int m = 0; m < 2; m++) {
         const pve_v16f ga = *(const pve_v16f *)(gam + 16 * m), be = *(const pve_v16f *)(bet + 16 * m);
@@ -467,7 +483,7 @@ __device__ __forceinline__ float actor_tile32(const pve_v8h *A1, const pve_v8h *
         }
         if (s == 4) {
             // ---- LayerNorm_1 + ReLU; K-block kb = 2 m + g of the next layer is exactly registers 8 g .. 8 g + 7 of h[m]
-            actor_ln_relu32(h, prm + PV_G1 + hf * 32, prm + PV_BE1 + hf * 32);
+            actor_ln_relu32(h, prm + PV_G1 + hf * 32, prm + PV_BE1 + hf * 32, prm[PV_EPS1]);
 #pragma unroll
             for (int kb = 0; kb < 4; kb++) {
                 float hv[8];
@@ -483,7 +499,7 @@ __device__ __forceinline__ float actor_tile32(const pve_v8h *A1, const pve_v8h *
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s % 2], bl[kb], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s % 2], bh[kb], acc, 0, 0, 0);
     }
-    actor_ln_relu32(g, prm + PV_G2 + hf * 32, prm + PV_BE2 + hf * 32);
+    actor_ln_relu32(g, prm + PV_G2 + hf * 32, prm + PV_BE2 + hf * 32, prm[PV_EPS2]);
     // ---- dense 64 -> 1, 3 tanh
     pve_v16f pv = g[0] * *(const pve_v16f *)(prm + PV_W3 + (hf * 2 + 0) * 16);
     pv = __builtin_elementwise_fma(g[1], *(const pve_v16f *)(prm + PV_W3 + (hf * 2 + 1) * 16), pv);
@@ -510,16 +526,39 @@ __device__ __forceinline__ void actor_fetch_env(const OBS_T *env_rows, int slot,
     for (int c = 0; c < 16; c++) x[c] = (c < 12 || !hf) ? (float)src[actor_feature(c, 0)] : 0.f;
 }
 
+// The pack-time scale of one dense layer.  mbits: the bit pattern of M = max |centred kernel| (a non-negative float32, so the
+// unsigned order of the patterns is the order of the values).  The centred kernel and the centred bias are multiplied by 2^e:
+// e = 0 while 2^-3 <= M <= 2^12 (and for M = 0 or not finite), else e = -floor(log2 M), clamped to +-40, which brings M into
+// [1, 2).  A power of two is exact in float32, and the LayerNorm that follows divides the factor out again -- provided its
+// variance epsilon is scaled by 4^e, which is what PV_EPS1 / PV_EPS2 hold.  tests/split_half_model.py `pack_exponent`.
+__device__ __forceinline__ int pack_exponent(unsigned mbits)
+{
+    const float m = __uint_as_float(mbits);
+    if (!(m < INFINITY) || m == 0.f || (m >= 0.125f && m <= 4096.f)) return 0;
+    int x;
+    (void)frexpf(m, &x);                                      // m = f 2^x, f in [0.5, 1): floor(log2 m) = x - 1 (subnormals too)
+    const int e = 1 - x;
+    return e > 40 ? 40 : e < -40 ? -40 : e;
+}
+
 // pve_set_actor: flat float32 weights -> the packed buffer (one workgroup of 256 threads)
 __global__ __launch_bounds__(256) void k_actor_pack(const float *__restrict__ W, unsigned char *__restrict__ packed)
 {
     __shared__ float cm1[ACT_IN], cm2[ACT_H], bm[2];
+    __shared__ unsigned mx[2];
     const int tid = threadIdx.x;
     // means over the OUTPUT units (what LayerNorm subtracts): per input row of each dense kernel, and of the biases
     if (tid < ACT_IN) { double s = 0; for (int u = 0; u < ACT_H; u++) s += (double)W[AW_W1 + tid * ACT_H + u]; cm1[tid] = (float)(s / ACT_H); }
     if (tid >= 64 && tid < 64 + ACT_H) { const int k = tid - 64; double s = 0; for (int u = 0; u < ACT_H; u++) s += (double)W[AW_W2 + k * ACT_H + u]; cm2[k] = (float)(s / ACT_H); }
     if (tid == 128 || tid == 129) { const int o = tid == 128 ? AW_B1 : AW_B2; double s = 0; for (int u = 0; u < ACT_H; u++) s += (double)W[o + u]; bm[tid - 128] = (float)(s / ACT_H); }
+    if (tid >= 192 && tid < 194) mx[tid - 192] = 0u;
     __syncthreads();
+    // the largest centred entry of each dense kernel -> the layer's factor 2^e (pack_exponent)
+    for (int n = tid; n < ACT_IN * ACT_H; n += 256) atomicMax(&mx[0], __float_as_uint(fabsf(W[AW_W1 + n] - cm1[n >> 6])));
+    for (int n = tid; n < ACT_H * ACT_H; n += 256) atomicMax(&mx[1], __float_as_uint(fabsf(W[AW_W2 + n] - cm2[n >> 6])));
+    __syncthreads();
+    const int e1 = pack_exponent(mx[0]), e2 = pack_exponent(mx[1]);
+    const float s1 = ldexpf(1.0f, e1), s2 = ldexpf(1.0f, e2);
     pve_v8h *A1 = (pve_v8h *)(packed + AP_A1), *A2 = (pve_v8h *)(packed + AP_A2);
     float *prm = (float *)(packed + AP_PRM);
     for (int n = tid; n < (4 + 8) * 64; n += 256) {           // one thread per operand vector (8 halves of one lane)
@@ -528,14 +567,14 @@ __global__ __launch_bounds__(256) void k_actor_pack(const float *__restrict__ W,
         if (t < 4) {                                          // layer 1: m = t >> 1, kb = t & 1: A[i][8 hf + e] = W1c[16 kb + 8 hf + e][32 m + i]
             const int m = t >> 1, kb = t & 1;
 #pragma unroll
-            for (int e = 0; e < 8; e++) { const int k = 16 * kb + 8 * hf + e; w[e] = k < ACT_IN ? W[AW_W1 + k * ACT_H + 32 * m + i] - cm1[k] : 0.f; }
+            for (int e = 0; e < 8; e++) { const int k = 16 * kb + 8 * hf + e; w[e] = k < ACT_IN ? (W[AW_W1 + k * ACT_H + 32 * m + i] - cm1[k]) * s1 : 0.f; }
             pve_v8h hi, lo;
             actor_split8(w, hi, lo);
             A1[((0 * 2 + m) * 2 + kb) * 64 + l] = hi; A1[((1 * 2 + m) * 2 + kb) * 64 + l] = lo;
         } else {                                              // layer 2: m2, kb: A[i][8 hf + e] = W2c[u(kb >> 1, 8 (kb & 1) + e, hf)][32 m2 + i]
             const int m2 = (t - 4) >> 2, kb = (t - 4) & 3;
 #pragma unroll
-            for (int e = 0; e < 8; e++) { const int k = actor_unit(kb >> 1, 8 * (kb & 1) + e, hf); w[e] = W[AW_W2 + k * ACT_H + 32 * m2 + i] - cm2[k]; }
+            for (int e = 0; e < 8; e++) { const int k = actor_unit(kb >> 1, 8 * (kb & 1) + e, hf); w[e] = (W[AW_W2 + k * ACT_H + 32 * m2 + i] - cm2[k]) * s2; }
             pve_v8h hi, lo;
             actor_split8(w, hi, lo);
             A2[((0 * 2 + m2) * 4 + kb) * 64 + l] = hi; A2[((1 * 2 + m2) * 4 + kb) * 64 + l] = lo;
@@ -543,15 +582,15 @@ __global__ __launch_bounds__(256) void k_actor_pack(const float *__restrict__ W,
     }
     if (tid < 64) {                                           // parameter vectors in lane order
         const int hf = tid >> 5, m = (tid >> 4) & 1, r = tid & 15, u = actor_unit(m, r, hf);
-        prm[PV_B1 + tid] = W[AW_B1 + u] - bm[0]; prm[PV_G1 + tid] = W[AW_LN1_G + u]; prm[PV_BE1 + tid] = W[AW_LN1_B + u];
-        prm[PV_B2 + tid] = W[AW_B2 + u] - bm[1]; prm[PV_G2 + tid] = W[AW_LN2_G + u]; prm[PV_BE2 + tid] = W[AW_LN2_B + u];
+        prm[PV_B1 + tid] = (W[AW_B1 + u] - bm[0]) * s1; prm[PV_G1 + tid] = W[AW_LN1_G + u]; prm[PV_BE1 + tid] = W[AW_LN1_B + u];
+        prm[PV_B2 + tid] = (W[AW_B2 + u] - bm[1]) * s2; prm[PV_G2 + tid] = W[AW_LN2_G + u]; prm[PV_BE2 + tid] = W[AW_LN2_B + u];
         prm[PV_W3 + tid] = W[AW_W3 + u];
     }
     if (tid < 32) {
         const int hf = tid >> 4, c = tid & 15, f = actor_feature(c, hf);
         prm[PV_LN0G + tid] = f < ACT_IN ? W[AW_LN0_G + f] : 0.f; prm[PV_LN0B + tid] = f < ACT_IN ? W[AW_LN0_B + f] : 0.f;
     }
-    if (tid == 0) { prm[PV_B3] = W[AW_B3]; prm[PV_A0] = 0.f; prm[PV_A0 + 1] = 0.f; prm[PV_A0 + 2] = 0.f; }
+    if (tid == 0) { prm[PV_B3] = W[AW_B3]; prm[PV_A0] = 0.f; prm[PV_EPS1] = 1e-12f * ldexpf(1.0f, 2 * e1); prm[PV_EPS2] = 1e-12f * ldexpf(1.0f, 2 * e2); }
     __threadfence();
     __syncthreads();
     if (tid < 64) {                                           // the action of an all-zero row (what a newly spawned vehicle gets)

@@ -98,7 +98,8 @@ inline float critic_canonical(const float *W, const float *x, const float *a7)
 // output units, split into half pairs, in A-operand order; parameter vectors in lane order) with a second layer of K = 71
 // padded to 80 = FIVE K-blocks of 16: blocks 0..3 are the hidden units exactly as in the actor, block 4 carries the 7
 // action rows of dense_1/kernel (k = 8 hf + e: rows 64 + e for hf = 0, e < 7) and zeros.  The float parameters use the
-// actor's PV_* offsets (PV_B3 = dense_2/bias; PV_A0 is unused).  Byte offsets:
+// actor's PV_* offsets (PV_B3 = dense_2/bias; PV_A0 is unused; PV_EPS1 / PV_EPS2 = the variance epsilons that go with the
+// pack-time factors 2^e of the two dense kernels, the seven action rows included -- pack_exponent of pve_actor.h).  Byte offsets:
 constexpr int CRT_KB2 = 5;
 constexpr int CP_A1 = 0;                                          // _Float16 [hl 2][m 2][kb 2][lane 64][8]
 constexpr int CP_A2 = CP_A1 + 2 * 2 * 2 * 64 * 8 * 2;             // _Float16 [hl 2][m2 2][kb 5][lane 64][8]
@@ -157,7 +158,7 @@ __device__ __forceinline__ float critic_tile32(const pve_v8h *A1, const pve_v8h 
         }
         if (s == 4) {
             // ---- LayerNorm_1 + ReLU; K-blocks 0..3 of the next layer are the registers of h (as in the actor), K-block 4 the actions
-            actor_ln_relu32(h, prm + PV_G1 + hf * 32, prm + PV_BE1 + hf * 32);
+            actor_ln_relu32(h, prm + PV_G1 + hf * 32, prm + PV_BE1 + hf * 32, prm[PV_EPS1]);
 #pragma unroll
             for (int kb = 0; kb < 4; kb++) {
                 float hv[8];
@@ -177,7 +178,7 @@ __device__ __forceinline__ float critic_tile32(const pve_v8h *A1, const pve_v8h 
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s % 2], bl[kb], acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s % 2], bh[kb], acc, 0, 0, 0);
     }
-    actor_ln_relu32(g, prm + PV_G2 + hf * 32, prm + PV_BE2 + hf * 32);
+    actor_ln_relu32(g, prm + PV_G2 + hf * 32, prm + PV_BE2 + hf * 32, prm[PV_EPS2]);
     // ---- dense 64 -> 1
     pve_v16f pv = g[0] * *(const pve_v16f *)(prm + PV_W3 + (hf * 2 + 0) * 16);
     pv = __builtin_elementwise_fma(g[1], *(const pve_v16f *)(prm + PV_W3 + (hf * 2 + 1) * 16), pv);
@@ -188,12 +189,20 @@ __device__ __forceinline__ float critic_tile32(const pve_v8h *A1, const pve_v8h 
 __global__ __launch_bounds__(256) void k_critic_pack(const float *__restrict__ W, unsigned char *__restrict__ packed)
 {
     __shared__ float cm1[ACT_IN], cm2[CRT_K2], bm[2];
+    __shared__ unsigned mx[2];
     const int tid = threadIdx.x;
     // means over the OUTPUT units (what LayerNorm subtracts): per input row of each dense kernel, and of the biases
     if (tid < ACT_IN) { double s = 0; for (int u = 0; u < ACT_H; u++) s += (double)W[CW_W1 + tid * ACT_H + u]; cm1[tid] = (float)(s / ACT_H); }
     if (tid >= 64 && tid < 64 + CRT_K2) { const int k = tid - 64; double s = 0; for (int u = 0; u < ACT_H; u++) s += (double)W[CW_W2 + k * ACT_H + u]; cm2[k] = (float)(s / ACT_H); }
     if (tid == 192 || tid == 193) { const int o = tid == 192 ? CW_B1 : CW_B2; double s = 0; for (int u = 0; u < ACT_H; u++) s += (double)W[o + u]; bm[tid - 192] = (float)(s / ACT_H); }
+    if (tid >= 194 && tid < 196) mx[tid - 194] = 0u;
     __syncthreads();
+    // the largest centred entry of each dense kernel, the seven action rows included -> the layer's factor 2^e (pack_exponent)
+    for (int n = tid; n < ACT_IN * ACT_H; n += 256) atomicMax(&mx[0], __float_as_uint(fabsf(W[CW_W1 + n] - cm1[n >> 6])));
+    for (int n = tid; n < CRT_K2 * ACT_H; n += 256) atomicMax(&mx[1], __float_as_uint(fabsf(W[CW_W2 + n] - cm2[n >> 6])));
+    __syncthreads();
+    const int e1 = pack_exponent(mx[0]), e2 = pack_exponent(mx[1]);
+    const float s1 = ldexpf(1.0f, e1), s2 = ldexpf(1.0f, e2);
     pve_v8h *A1 = (pve_v8h *)(packed + CP_A1), *A2 = (pve_v8h *)(packed + CP_A2);
     float *prm = (float *)(packed + CP_PRM);
     for (int n = tid; n < CRT_BLOCKS * 64; n += 256) {        // one thread per operand vector (8 halves of one lane)
@@ -203,7 +212,7 @@ __global__ __launch_bounds__(256) void k_critic_pack(const float *__restrict__ W
         if (t < 4) {                                          // layer 1: A[i][8 hf + e] = W1c[16 kb + 8 hf + e][32 m + i]
             const int m = t >> 1, kb = t & 1;
 #pragma unroll
-            for (int e = 0; e < 8; e++) { const int k = 16 * kb + 8 * hf + e; w[e] = k < ACT_IN ? W[CW_W1 + k * ACT_H + 32 * m + i] - cm1[k] : 0.f; }
+            for (int e = 0; e < 8; e++) { const int k = 16 * kb + 8 * hf + e; w[e] = k < ACT_IN ? (W[CW_W1 + k * ACT_H + 32 * m + i] - cm1[k]) * s1 : 0.f; }
             actor_split8(w, hi, lo);
             A1[((0 * 2 + m) * 2 + kb) * 64 + l] = hi; A1[((1 * 2 + m) * 2 + kb) * 64 + l] = lo;
         } else {                                              // layer 2: kb < 4 the hidden units (as the actor), kb = 4 the action rows
@@ -211,7 +220,7 @@ __global__ __launch_bounds__(256) void k_critic_pack(const float *__restrict__ W
 #pragma unroll
             for (int e = 0; e < 8; e++) {
                 const int k = kb < 4 ? actor_unit(kb >> 1, 8 * (kb & 1) + e, hf) : ((hf == 0 && e < CRT_ACT) ? ACT_H + e : -1);
-                w[e] = k >= 0 ? W[CW_W2 + k * ACT_H + 32 * m2 + i] - cm2[k] : 0.f;
+                w[e] = k >= 0 ? (W[CW_W2 + k * ACT_H + 32 * m2 + i] - cm2[k]) * s2 : 0.f;
             }
             actor_split8(w, hi, lo);
             A2[((0 * 2 + m2) * CRT_KB2 + kb) * 64 + l] = hi; A2[((1 * 2 + m2) * CRT_KB2 + kb) * 64 + l] = lo;
@@ -219,15 +228,15 @@ __global__ __launch_bounds__(256) void k_critic_pack(const float *__restrict__ W
     }
     if (tid < 64) {                                           // parameter vectors in lane order
         const int hf = tid >> 5, m = (tid >> 4) & 1, r = tid & 15, u = actor_unit(m, r, hf);
-        prm[PV_B1 + tid] = W[CW_B1 + u] - bm[0]; prm[PV_G1 + tid] = W[CW_LN1_G + u]; prm[PV_BE1 + tid] = W[CW_LN1_B + u];
-        prm[PV_B2 + tid] = W[CW_B2 + u] - bm[1]; prm[PV_G2 + tid] = W[CW_LN2_G + u]; prm[PV_BE2 + tid] = W[CW_LN2_B + u];
+        prm[PV_B1 + tid] = (W[CW_B1 + u] - bm[0]) * s1; prm[PV_G1 + tid] = W[CW_LN1_G + u]; prm[PV_BE1 + tid] = W[CW_LN1_B + u];
+        prm[PV_B2 + tid] = (W[CW_B2 + u] - bm[1]) * s2; prm[PV_G2 + tid] = W[CW_LN2_G + u]; prm[PV_BE2 + tid] = W[CW_LN2_B + u];
         prm[PV_W3 + tid] = W[CW_W3 + u];
     }
     if (tid < 32) {
         const int hf = tid >> 4, c = tid & 15, f = actor_feature(c, hf);
         prm[PV_LN0G + tid] = f < ACT_IN ? W[CW_LN0_G + f] : 0.f; prm[PV_LN0B + tid] = f < ACT_IN ? W[CW_LN0_B + f] : 0.f;
     }
-    if (tid == 0) { prm[PV_B3] = W[CW_B3]; prm[PV_A0] = 0.f; prm[PV_A0 + 1] = 0.f; prm[PV_A0 + 2] = 0.f; }
+    if (tid == 0) { prm[PV_B3] = W[CW_B3]; prm[PV_A0] = 0.f; prm[PV_EPS1] = 1e-12f * ldexpf(1.0f, 2 * e1); prm[PV_EPS2] = 1e-12f * ldexpf(1.0f, 2 * e2); }
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -142,9 +142,10 @@ def load_graph_golden():
     return rows, z["kinds"], z["actions_f32"], z["actions_f64"], json.loads(str(z["meta"])), ~const_nonzero
 
 
-def planted_batch(backend, n_envs, ticks=150, rate=1000.0, seed=31, **cfg):
-    """A batch in a filled state (closed loop with the installed actor for `ticks` ticks) whose controlled slots the
-    callers overwrite with golden rows.  Returns (batch, [(env, slot)] of the controlled slots)."""
+def planted_batch(backend, n_envs, ticks=150, rate=1000.0, seed=31, weights=None, **cfg):
+    """A batch in a filled state (closed loop with the shipped actor for `ticks` ticks) whose controlled slots the
+    callers overwrite with golden rows.  weights: the actor (a dict) the batch is left with; default: the shipped one.
+    Returns (batch, [(env, slot)] of the controlled slots)."""
     from pve_mcc_amd.arrivals import synthetic_arrivals
     arr = synthetic_arrivals(n_envs, rate=rate, horizon_s=ticks * 0.1 + 40, seed=seed)
     b = make_batch(arr, n_envs, 128, backend, outputs=("obs_post", "reward", "flags", "env_out", "new_slot"), **cfg)
@@ -152,6 +153,8 @@ def planted_batch(backend, n_envs, ticks=150, rate=1000.0, seed=31, **cfg):
     b.set_actor(flat_weights(load_weights()))
     for _ in range(ticks):
         b.step_with_actor()
+    if weights is not None:
+        b.set_actor(flat_weights(weights))
     ctl = _np(b.control_mask())
     return b, np.argwhere(ctl)
 
