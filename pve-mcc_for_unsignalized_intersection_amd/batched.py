@@ -403,7 +403,8 @@ class BatchedIntersections:
         windows a Done truncates (the reference drops all but the oldest).  max_records=None reads `total` once (one
         synchronisation) and allocates exactly, M = total; a given max_records allocates that many rows without synchronising,
         fills the first min(total, max_records) in order and returns `total` as a 0-dim device tensor.
-        lane_num 4 / 8: the pass is slot-indexed; that `ids` order differs from slot order there does not matter."""
+        lane_num 4 / 8: the pass is slot-indexed; that `ids` order differs from slot order there does not matter
+        (tests/nstep_identity_scenarios.py holds it to the reference's per-vehicle buffers, keyed by vehicle id, on those layouts)."""
         window = int(window)
         with self._own_stream():
             stamped = cur is None
