@@ -6,7 +6,8 @@
 // dead-lock walk, the observation rows) run on a second, dense mapping: thread t also works for the
 // t-th controlled vehicle of the intersection (slot_of[t]).  With ~50 controlled among ~85 alive vehicles
 // in 128 slots all of them fall into the first wave, and the second wave skips those phases (its
-// instructions were issued for a dozen active lanes before).  The reference's order-dependent
+// instructions were issued for a dozen active lanes before; the HOME block hands it two LDS-only side jobs of those phases
+// instead: Shared::SIDE).  The reference's order-dependent
 // (Gauss-Seidel) semantics are turned into closed-form parallel rules:
 //   S1-S3  step()            ref traffic_interaction_scene.py:1501-1539  (in-lane brake chain)
 //   SCAN   scene_update()    ref :233-334  (virtual lane, predecessor, 6 nearest, reward, XY hit)
@@ -406,6 +407,14 @@ template <int CAP, bool LJ = (CAP == 128), bool HOME_ = false, int POOL_ = (HOME
 struct Shared : std::conditional<HOME_, Homes<CAP>, HomesOff<CAP>>::type {
     static constexpr int NW = CAP / 64;
     static constexpr bool HOME = HOME_;
+    // SIDE jobs (HOME only): in the dense phases the second wave has next to nothing of its own to do, so work
+    // whose inputs and outputs all live in LDS leaves the critical chain of the first wave: thread t computes the
+    // single-precision position (BUILD) of dense vehicle t ^ 64 and refreshes the stale head (WALK) of lane t - 64.  With
+    // <= 64 controlled vehicles both jobs run in the second wave only; beyond, the first wave works for the dense vehicles 64..
+    // of the second.  A side thread reads slot_of[] / lane_of[] / p[] itself: r.ds / r.dlane / r.dp belong to the dense
+    // vehicle of its own index.
+    static constexpr bool SIDE = HOME_;
+    static_assert(!SIDE || CAP == 128, "side jobs: thread t works for index t ^ 64 (two waves)");
     static_assert(!HOME_ || (POOL_ * 4 >= 2 * CAP * 4 + CAP + 1 && POOL_ >= CAP && POOL_ % 8 == 0), "HOME: the staging overlays need 2 CAP ints + CAP + 1 bytes of s_idx");
     static constexpr bool PIN_READS = true;   // walk_window: keep the batched window reads from being sunk into guarded blocks
     static constexpr int POOL = POOL_;
@@ -1058,14 +1067,24 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
         // (HOME: S3 has done it; an uncontrolled vehicle's vir_dis stays where it is)
         if constexpr (!Sh::HOME) sh.virdis[t] = (r.alive && r.ctl) ? r.jerk : r.vir_dis;
         // ---- dense mapping from here: thread t works for the t-th controlled vehicle
-        r.dctl = t < mask_count<NW>(sh.m_ctl);
+        const int n_ctl = mask_count<NW>(sh.m_ctl);
+        r.dctl = t < n_ctl;
         r.ds = 0; r.dlane = 0; r.dp = 0;
+        if constexpr (Sh::SIDE) {
+            // side job: the single-precision position of dense vehicle t ^ 64 (~45 dependent instructions, read by REWARD two
+            // barriers from here), while that vehicle's dense thread -- a lane of the other wave -- files its list entries
+            const int sc = t ^ 64;
+            if (sc < n_ctl) {
+                const int ss = sh.slot_of[sc];
+                get_xy_f32(c, sh.p[ss], sh.lane_of[ss], sh.xy32[ss][0], sh.xy32[ss][1]);
+            }
+        }
         if (!r.dctl) return;
         const int sl = sh.slot_of[t];
         const int lane = sh.lane_of[sl];
         const double p = sh.p[sl];
         r.ds = sl; r.dlane = lane; r.dp = p;
-        get_xy_f32(c, p, lane, sh.xy32[sl][0], sh.xy32[sl][1]);
+        if constexpr (!Sh::SIDE) get_xy_f32(c, p, lane, sh.xy32[sl][0], sh.xy32[sl][1]);
     }
     // the entries of the lists [d0, d1) (HOME: one group of lists per pass; else all twelve)
     // GRP = false: every list in one pass (the rule, and the only form of the blocks with a 5 CAP pool): no group arithmetic at all
@@ -1497,26 +1516,30 @@ template <int CAP, class ShT = Shared<CAP>> struct Tick {
         // The valid bits of the rebuilt lists are combined by two ballots and ONE read-modify-write of the header word: an LDS
         // atomic or / and per lane on that one word is expanded by the compiler's atomic optimizer into a scalar loop over the
         // active lanes (s_ff1 / v_readlane / ... : ~7 instructions x 12 lanes on the first wave's path, every tick)
-        const bool rebuilt = t < NL && sh.hd.lane_start[t < NL ? t + 1 : 0] > sh.hd.lane_start[t < NL ? t : 0] &&
-                             (!GRP || (t >= d0 && t < d1));
+        // SIDE: the head of lane d is the side job of thread 64 + d -- lanes 0..11 of the SECOND wave, idle from here to the
+        // barrier behind REWARD -- so that its three dependent LDS trips do not stand in front of the first wave's window walk
+        // (written as t - 64 with NL for the first wave: the `t ^ 64` form costs the pool-source kernel 20 spilled registers)
+        const int d = Sh::SIDE ? (t >= 64 ? t - 64 : NL) : t;
+        const bool rebuilt = d < NL && sh.hd.lane_start[d < NL ? d + 1 : 0] > sh.hd.lane_start[d < NL ? d : 0] &&
+                             (!GRP || (d >= d0 && d < d1));
         bool hvalid = false;
         if (rebuilt) {
-            const int base = sh.loff[t] - gb;
-            if (sh.nfin[t] > 0) {
+            const int base = sh.loff[d] - gb;
+            if (sh.nfin[d] > 0) {
                 const int hr = Sh::DIRECT ? sh.s_slot[Sh::DIRECT ? base : 0] : sh.u_slot[sidx_at(sh.s_idx, base)];
                 hvalid = true;
                 int hl = sh.lane_of[hr];
-                sh.hd.head_lane[t] = hl;
-                sh.hd.head_j[t] = hr - sh.hd.lane_start[hl];
+                sh.hd.head_lane[d] = hl;
+                sh.hd.head_j[d] = hr - sh.hd.lane_start[hl];
             }
         }
 #if PVE_DEVICE_CODE
         {
-            const unsigned mr = (unsigned)__ballot(rebuilt), mv = (unsigned)__ballot(hvalid);   // (lanes 0..11 of the first wave; 0 elsewhere)
-            if (t == 0) sh.hd.head_valid = (sh.hd.head_valid & ~(int)mr) | (int)mv;
+            const unsigned mr = (unsigned)__ballot(rebuilt), mv = (unsigned)__ballot(hvalid);   // (lanes 0..11 of one wave; 0 elsewhere)
+            if (d == 0) sh.hd.head_valid = (sh.hd.head_valid & ~(int)mr) | (int)mv;
         }
 #else
-        if (rebuilt) { if (hvalid) sh.hd.head_valid |= 1 << t; else sh.hd.head_valid &= ~(1 << t); }
+        if (rebuilt) { if (hvalid) sh.hd.head_valid |= 1 << d; else sh.hd.head_valid &= ~(1 << d); }
 #endif
         if (!r.dctl) return;
         const int sl = r.ds, lane = r.dlane;
