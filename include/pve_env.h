@@ -426,7 +426,8 @@ int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t
  * in float32 (csrc/pve_learn.h).  losses [n_batches][2] = critic, actor loss of each step, or NULL; grads
  * [n_batches][6841 + 6393] = the gradients each step applied, critic then actor, or NULL.  PVE_LEARN_CRITIC_ONLY skips 2. and the
  * actor's soft update (actor loss and gradients are reported as 0).
- * NOT reproduced: td_error / update_priority (main.py:76-79; dead with rand_s = True) and the summaries.  The reference assigns
+ * Not part of the step: td_error / update_priority (main.py:76-79; dead with rand_s = True) are pve_critic_forward on the sampled
+ * rows + pve_prio_update (below); the summaries are NOT reproduced.  The reference assigns
  * self.critic_lr after the optimizer is built, which changes nothing there; here both learning rates are read on every call.
  * block_threads: 0 = 1024; else a multiple of 64 up to 1024 (same results).
  * Errors (PVE_ERR_INVALID): null pointers, batch < 1, n_batches < 1, batch * n_batches > 2^31 - 1, params / rows / networks not
@@ -480,6 +481,76 @@ int pve_learner_step(pve_handle h, const pve_learner *lrn, const float *rows, co
 int pve_learner_step_wide(pve_handle h, const pve_learner *lrn, const float *rows, const float *act7, const float *target,
                           int64_t batch, int64_t n_batches, float *work, int64_t work_floats, int32_t groups,
                           float *losses /* or NULL */, float *grads /* or NULL */);
+
+/* RANK-BASED PRIORITISED REPLAY on the device: the memory the reference builds in every run (replay_buffer.py:13-18 constructs
+ * rank_based.Experience) and draws from with rand_s = False (replay_buffer.py:24, rank_based.py:148-188 `sample`), with the update
+ * main.py:76-79 makes from the target critic (`td_error = |target_Q(obs, act, other) - target|`, `update_priority`).  Additive
+ * within ABI 9: five new symbols and one new struct, nothing existing changes, PVE_ABI_VERSION stays 9; a binding detects an older
+ * library by the missing symbols.  The specification is csrc/pve_prio.h (host + device), restated in NumPy as
+ * PrioritizedReplayModel (pve_mcc_amd/replay.py).  Every integer part is bit-exact; the only floating-point arithmetic is the
+ * update's one subtraction (exact IEEE) and the importance weight.
+ *
+ * `replay` is the ring of pve_replay (reset, appended to and counted through the pve_replay_* calls, unchanged) with
+ * capacity = the reference's `size`: rank_based.py:82-99 cycles its index over 1 .. size (e_id = slot + 1, slot = w mod capacity).
+ * PRIORITY STORE (caller-owned DEVICE memory): prio uint32 [capacity] = the bit pattern of a non-negative float32; pseq int64
+ * [capacity].  The priority of slot s is valid only if pseq[s] is the record number living in s now; otherwise the record is NEW
+ * and ranks as +inf (rank_based.py:114-117: a new record gets the heap's maximum).  pstate int64 [PVE_PRIO_STATE_WORDS]:
+ * pstate[0] = pdraws (minibatches ever drawn), [1] = live records seen by the latest ranking, [2] = its partition index,
+ * [3] = ids ignored by the latest update.
+ * pve_prio_reset fills pseq with -1 and zeroes pstate (it does not touch the ring: pve_replay_reset does).
+ * pve_prio_rank (binary_heap.py:194-221 `balance_tree` / `priority_to_experience`) writes order int32 [L]: order[r] = the age
+ * index of the record of rank r + 1 among the L = min(written, capacity) live records, sorted descending by (priority bits, record
+ * number) -- a total order; NEW records first, newest first.  For pairwise distinct priorities this is the reference's
+ * priority_to_experience(1 .. L) after rebalance(); the reference's order among ties follows its heap layout and is NOT reproduced.
+ * The result is a pure function of the memory's contents (not of block_threads or of what the scratch held).
+ * STRATA TABLES, built by the caller as rank_based.py:40-80: part_from int64 [32] (HOST) = for k = 0 .. 31 the smallest L with
+ * floor(1.0 * L / size * 32) >= k + 1 (rank_based.py:159; unused trailing entries may be 2^62); the partition index of L is the
+ * number of thresholds <= L, partition p >= 1 uses row p - 1 of ends int32 [32][batch + 1] (`strata_ends`: ends[0] = 0,
+ * ends[batch] = n_p = p * floor(size / 32)).  `ends` is the DEVICE copy the kernel reads, `ends_host` the same table in HOST memory,
+ * which every call validates (each row starts at 0 and is non-decreasing within 0 .. capacity).
+ * pve_prio_sample (rank_based.py:148-188) ranks first, always, then draws minibatches d = pdraws, pdraws + 1, ..: stratum j =
+ * 0 .. batch - 1 takes  lo = min(ends[j] + 1, ends[j + 1]), hi = max(ends[j] + 1, ends[j + 1])  (rank_based.py:167-172, the swapped
+ * randint of degenerate strata included: ranks may repeat within a minibatch),  rank = lo + mulhi32(u, hi - lo + 1)  with u = word 0
+ * of Philox4x32-10, counter = (j, 0, d low word, d high word), key = (seed low word ^ 0x5052494F, seed high word ^ 0x52414E4B),
+ * clamped to 1 .. L (inactive for tables built as above).  The record is age index order[rank - 1], record number written - L + age.
+ * The reference's Mersenne-Twister draw is not reproduced.  Outputs: rows / act7 / target / seq as pve_replay_sample writes them,
+ * rank int32 [n_batches][batch], weight float32 [n_batches][batch] = (rank / rank_max)^alpha_beta with rank_max the minibatch's
+ * largest rank (rank_based.py:176-182 with the normaliser and partition_max cancelled; alpha_beta = alpha * beta as one float32).
+ * With L < min_live, or L below part_from[0], the call is short: seq = -1 and zeros, pdraws unchanged; pstate[1] = L either way.
+ * pve_prio_update (main.py:76-79, rank_based.py:138-146) stores p = |q[i] - target[i]| in float32 (|q[i]| when target is NULL; NaN
+ * is stored as +inf) as the priority of record seq[i], i < n.  An id outside [written - L, written) -- -1, or a record overwritten
+ * since -- is ignored and counted in pstate[3] (the reference would write onto the slot's new occupant).  Of an id named several
+ * times in one call the largest p wins; the old value is replaced, not maxed.
+ * scratch: caller-owned DEVICE memory of scratch_bytes >= pve_prio_scratch_bytes(capacity), 16-byte aligned, for the ranking; it
+ * needs no initialisation and must not be shared by calls on different streams.  pve_prio_scratch_bytes returns 0 for a capacity
+ * outside 1 .. 2^31 - 1.  replay.block_threads: diagnostics as in pve_replay (same results).
+ * Errors (PVE_ERR_INVALID): what pve_replay_* reject in `replay`; null prio / pseq / order / pstate / scratch / ends / ends_host /
+ * part_from / outputs / seq / q; scratch not 16-byte aligned (pseq, pstate, seq: 8; the others: 4; rows and act7: 16); a
+ * scratch_bytes too small; batch outside 1 .. capacity; part_from below 1 or decreasing; an `ends_host` row that does not start
+ * at 0, decreases or passes capacity; n_batches < 1; batch * n_batches > 2^31 - 1; min_live < 0; alpha_beta negative or not
+ * finite; n < 0; a backend without the kernels.  All calls are asynchronous on the handle's stream, none synchronises. */
+#define PVE_PRIO_STATE_WORDS 4
+#define PVE_PRIO_PARTS 32
+typedef struct pve_prio {
+    pve_replay replay;            /* the ring; capacity = the reference's `size` */
+    uint32_t *prio;               /* DEVICE [capacity] */
+    int64_t *pseq;                /* DEVICE [capacity] */
+    int32_t *order;               /* DEVICE [capacity] */
+    int64_t *pstate;              /* DEVICE [PVE_PRIO_STATE_WORDS] */
+    void *scratch;                /* DEVICE [scratch_bytes] */
+    int64_t scratch_bytes;
+    const int32_t *ends;          /* DEVICE [PVE_PRIO_PARTS][batch + 1] */
+    const int32_t *ends_host;     /* HOST   [PVE_PRIO_PARTS][batch + 1], the same table */
+    const int64_t *part_from;     /* HOST   [PVE_PRIO_PARTS] */
+    int64_t batch;
+} pve_prio;
+size_t pve_prio_scratch_bytes(int64_t capacity);
+int pve_prio_reset(pve_handle h, const pve_prio *pp);
+int pve_prio_rank(pve_handle h, const pve_prio *pp);
+int pve_prio_sample(pve_handle h, const pve_prio *pp, int64_t n_batches, int64_t min_live, float alpha_beta, float *rows,
+                    float *act7, float *target, int64_t *seq, int32_t *rank, float *weight);
+int pve_prio_update(pve_handle h, const pve_prio *pp, const int64_t *seq, const float *q, const float *target /* or NULL */,
+                    int64_t n);
 
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly

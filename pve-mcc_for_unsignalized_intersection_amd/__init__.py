@@ -3,8 +3,9 @@ Mingtzge/PVE-MCC_for_unsignalized_intersection): Python host code over hand-writ
 behind a C ABI (include/pve_env.h -> libpveenv.so)."""
 from ._capi import PveError, load_library  # noqa: F401
 from .batched import BatchedIntersections, PipelinedIntersections  # noqa: F401
-from .replay import ReplayMemory, ReplayModel  # noqa: F401
+from .replay import PrioritizedReplayMemory, PrioritizedReplayModel, ReplayMemory, ReplayModel  # noqa: F401
 from .learner import Learner, LearnerModel  # noqa: F401
 
-__all__ = ["BatchedIntersections", "Learner", "LearnerModel", "PipelinedIntersections", "PveError", "ReplayMemory", "ReplayModel",
+__all__ = ["BatchedIntersections", "Learner", "LearnerModel", "PipelinedIntersections", "PrioritizedReplayMemory", "PrioritizedReplayModel",
+           "PveError", "ReplayMemory", "ReplayModel",
            "load_library"]

@@ -25,6 +25,7 @@ PVE_ACTOR_N_WEIGHTS = 6393
 PVE_CRITIC_N_WEIGHTS = 6841
 NSTEP_TAIL, NSTEP_MAX_WINDOW, NSTEP_RECORD = 0x1, 16, 36
 REPLAY_STATE_WORDS = 4
+PRIO_STATE_WORDS, PRIO_PARTS = 4, 32
 LEARN_SLICE, LEARNER_WIDE_ROW = 128, 13244
 ABI_VERSION = 9
 SRC_ZERO, SRC_POOL, SRC_ACTOR, SRC_TABLE = 0, 1, 2, 3
@@ -77,6 +78,12 @@ class PveReplay(C.Structure):
                 ("block_threads", C.c_int32)]
 
 
+class PvePrio(C.Structure):
+    _fields_ = [("replay", PveReplay), ("prio", C.c_void_p), ("pseq", C.c_void_p), ("order", C.c_void_p), ("pstate", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64), ("ends", C.c_void_p), ("ends_host", C.c_void_p),
+                ("part_from", C.c_void_p), ("batch", C.c_int64)]
+
+
 class PveLearner(C.Structure):
     _fields_ = [("params", C.c_void_p), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
                 ("beta2", C.c_float), ("epsilon", C.c_float), ("tau", C.c_float), ("flags", C.c_int32), ("block_threads", C.c_int32)]
@@ -105,7 +112,7 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise",
            "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather",
            "pve_replay_reset", "pve_replay_append", "pve_replay_sample", "pve_learner_init", "pve_learner_step",
-           "pve_learner_step_wide")
+           "pve_learner_step_wide", "pve_prio_scratch_bytes", "pve_prio_reset", "pve_prio_rank", "pve_prio_sample", "pve_prio_update")
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -149,10 +156,16 @@ def _declare(L):
     L.pve_learner_init.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, vp]
     L.pve_learner_step.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
     L.pve_learner_step_wide.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp]
+    L.pve_prio_scratch_bytes.restype = C.c_size_t
+    L.pve_prio_scratch_bytes.argtypes = [C.c_int64]
+    L.pve_prio_reset.argtypes = [vp, C.POINTER(PvePrio)]
+    L.pve_prio_rank.argtypes = [vp, C.POINTER(PvePrio)]
+    L.pve_prio_sample.argtypes = [vp, C.POINTER(PvePrio), C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp]
+    L.pve_prio_update.argtypes = [vp, C.POINTER(PvePrio), vp, vp, vp, C.c_int64]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
     for name in EXPORTS:
-        if name not in ("pve_last_error", "pve_workspace_bytes", "pve_default_config"):
+        if name not in ("pve_last_error", "pve_workspace_bytes", "pve_default_config", "pve_prio_scratch_bytes"):
             getattr(L, name).restype = C.c_int
     L.pve_default_config.restype = None
     return L

@@ -48,6 +48,14 @@
 //     static int   launch_replay_sample(const pve::ReplayArgs &, long long batch, long long n_batches, float *rows, float *act7,
 //                                       float *target, long long *seq, int block_threads, void *stream, std::string &err);
 //                                                // optional, both or none: pve_replay_reset / _append / _sample (csrc/pve_replay.h)
+//     static int   launch_prio_reset(const pve::PrioArgs &, int block_threads, void *stream, std::string &err);
+//     static int   launch_prio_rank(const pve::PrioArgs &, int block_threads, void *stream, std::string &err);
+//     static int   launch_prio_sample(const pve::PrioArgs &, long long n_batches, long long min_live, float alpha_beta, float *rows,
+//                                     float *act7, float *target, long long *seq, int32_t *rank, float *weight, int block_threads,
+//                                     void *stream, std::string &err);          // ranks first
+//     static int   launch_prio_update(const pve::PrioArgs &, const long long *seq, const float *q, const float *target, long long n,
+//                                     int block_threads, void *stream, std::string &err);
+//                                                // optional, all four or none: pve_prio_reset / _rank / _sample / _update (csrc/pve_prio.h)
 //     static int   launch_learner_init(float *params, const float *actor, const float *critic, const float *target_actor,
 //                                      const float *target_critic, float beta1, float beta2, void *stream, std::string &err);
 //     static int   launch_learner_step(const pve::LearnCtx &, int block_threads, void *stream, std::string &err);
@@ -260,6 +268,29 @@ template <class B> struct backend_replay<B, decltype((void)&B::launch_replay_sam
     {
         return B::launch_replay_sample(A, batch, n_batches, rows, act7, target, seq, block, stream, err);
     }
+};
+// The prioritised memory (pve_prio_reset / _rank / _sample / _update) needs the kernels of pve_prio.h: Backend::launch_prio_reset /
+// launch_prio_rank / launch_prio_sample / launch_prio_update (detected by the third).  A backend without them exports the entry
+// points all the same; they validate their arguments and then refuse with PVE_ERR_INVALID.
+template <class B, class = void> struct backend_prio {
+    static constexpr bool value = false;
+    static int reset(const PrioArgs &, int, void *, std::string &) { return -1; }
+    static int rank(const PrioArgs &, int, void *, std::string &) { return -1; }
+    static int sample(const PrioArgs &, long long, long long, float, float *, float *, float *, long long *, int32_t *, float *, int, void *,
+                      std::string &) { return -1; }
+    static int update(const PrioArgs &, const long long *, const float *, const float *, long long, int, void *, std::string &) { return -1; }
+};
+template <class B> struct backend_prio<B, decltype((void)&B::launch_prio_sample)> {
+    static constexpr bool value = true;
+    static int reset(const PrioArgs &A, int block, void *stream, std::string &err) { return B::launch_prio_reset(A, block, stream, err); }
+    static int rank(const PrioArgs &A, int block, void *stream, std::string &err) { return B::launch_prio_rank(A, block, stream, err); }
+    static int sample(const PrioArgs &A, long long n_batches, long long min_live, float alpha_beta, float *rows, float *act7, float *target,
+                      long long *seq, int32_t *rank, float *weight, int block, void *stream, std::string &err)
+    {
+        return B::launch_prio_sample(A, n_batches, min_live, alpha_beta, rows, act7, target, seq, rank, weight, block, stream, err);
+    }
+    static int update(const PrioArgs &A, const long long *seq, const float *q, const float *target, long long n, int block, void *stream,
+                      std::string &err) { return B::launch_prio_update(A, seq, q, target, n, block, stream, err); }
 };
 // The learner step (pve_learner_init / pve_learner_step) needs the kernels behind Backend::launch_learner_init /
 // launch_learner_step (detected by the second).  A backend without them exports the entry points all the same; they validate
@@ -722,6 +753,112 @@ int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t
     if (backend_replay<Backend>::sample(A, (long long)batch, (long long)n_batches, rows, act7, target, (long long *)seq, rp->block_threads,
                                         h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_replay_sample: " + err);
+    return PVE_OK;
+}
+
+// pve_prio -> PrioArgs, with the checks the four entry points share
+static int prio_args(pve_handle h, const pve_prio *pp, const char *who, PrioArgs &A)
+{
+    const std::string w(who);
+    if (!h || !pp) return fail(PVE_ERR_INVALID, w + ": null argument");
+    const int rc = replay_args(h, &pp->replay, who, A.R);
+    if (rc != PVE_OK) return rc;
+    if (!pp->prio || !pp->pseq || !pp->order || !pp->pstate || !pp->scratch || !pp->ends || !pp->ends_host || !pp->part_from)
+        return fail(PVE_ERR_INVALID, w + ": null prio, pseq, order, pstate, scratch, ends, ends_host or part_from");
+    if (((uintptr_t)pp->prio & 3) || ((uintptr_t)pp->order & 3) || ((uintptr_t)pp->ends & 3) || ((uintptr_t)pp->pseq & 7) ||
+        ((uintptr_t)pp->pstate & 7) || ((uintptr_t)pp->scratch & 15))
+        return fail(PVE_ERR_INVALID, w + ": scratch must be 16-byte aligned, pseq and pstate 8-byte, prio, order and ends 4-byte aligned");
+    if (pp->scratch_bytes < 0 || (uint64_t)pp->scratch_bytes < (uint64_t)prio_scratch_bytes(A.R.capacity))
+        return fail(PVE_ERR_INVALID, w + ": scratch_bytes is below pve_prio_scratch_bytes(capacity)");
+    if (pp->batch < 1 || pp->batch > A.R.capacity) return fail(PVE_ERR_INVALID, w + ": batch must be 1 .. capacity");
+    for (int k = 0; k < PRIO_PARTS; k++) {
+        if (pp->part_from[k] < 1 || (k > 0 && pp->part_from[k] < pp->part_from[k - 1]))
+            return fail(PVE_ERR_INVALID, w + ": part_from must be >= 1 and non-decreasing");
+        const int32_t *row = pp->ends_host + (size_t)k * (size_t)(pp->batch + 1);
+        if (row[0] != 0) return fail(PVE_ERR_INVALID, w + ": every row of ends must start at 0");
+        for (int64_t j = 1; j <= pp->batch; j++)
+            if (row[j] < row[j - 1] || row[j] > A.R.capacity)
+                return fail(PVE_ERR_INVALID, w + ": every row of ends must be non-decreasing within 0 .. capacity");
+        A.part_from[k] = pp->part_from[k];
+    }
+    A.prio = pp->prio; A.pseq = (long long *)pp->pseq; A.order = pp->order; A.pstate = (long long *)pp->pstate;
+    A.ends = pp->ends; A.batch = pp->batch;
+    prio_carve_scratch(A, pp->scratch);
+    return PVE_OK;
+}
+
+static int no_prio_kernels(const char *who)
+{
+    return fail(PVE_ERR_INVALID, std::string(who) + ": this backend has no prioritised replay kernels");
+}
+
+size_t pve_prio_scratch_bytes(int64_t capacity)
+{
+    return capacity < 1 || capacity > 0x7fffffffLL ? 0 : prio_scratch_bytes(capacity);
+}
+
+int pve_prio_reset(pve_handle h, const pve_prio *pp)
+{
+    PrioArgs A;
+    const int rc = prio_args(h, pp, "pve_prio_reset", A);
+    if (rc != PVE_OK) return rc;
+    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_reset");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_prio<Backend>::reset(A, pp->replay.block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_prio_reset: " + err);
+    return PVE_OK;
+}
+
+int pve_prio_rank(pve_handle h, const pve_prio *pp)
+{
+    PrioArgs A;
+    const int rc = prio_args(h, pp, "pve_prio_rank", A);
+    if (rc != PVE_OK) return rc;
+    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_rank");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_prio<Backend>::rank(A, pp->replay.block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_prio_rank: " + err);
+    return PVE_OK;
+}
+
+int pve_prio_sample(pve_handle h, const pve_prio *pp, int64_t n_batches, int64_t min_live, float alpha_beta, float *rows, float *act7,
+                    float *target, int64_t *seq, int32_t *rank, float *weight)
+{
+    PrioArgs A;
+    const int rc = prio_args(h, pp, "pve_prio_sample", A);
+    if (rc != PVE_OK) return rc;
+    if (n_batches < 1 || n_batches > 0x7fffffffLL / pp->batch)
+        return fail(PVE_ERR_INVALID, "pve_prio_sample: n_batches must be >= 1 and batch * n_batches <= 2^31 - 1");
+    if (min_live < 0) return fail(PVE_ERR_INVALID, "pve_prio_sample: min_live must be >= 0");
+    if (!(alpha_beta >= 0.f && alpha_beta <= 3.4028234663852886e38f))
+        return fail(PVE_ERR_INVALID, "pve_prio_sample: alpha_beta must be finite and >= 0");
+    if (!rows || !act7 || !target || !seq || !rank || !weight) return fail(PVE_ERR_INVALID, "pve_prio_sample: null output");
+    if (((uintptr_t)rows & 15) || ((uintptr_t)act7 & 15) || ((uintptr_t)target & 3) || ((uintptr_t)seq & 7) || ((uintptr_t)rank & 3) ||
+        ((uintptr_t)weight & 3))
+        return fail(PVE_ERR_INVALID, "pve_prio_sample: rows and act7 must be 16-byte aligned, seq 8-byte, target, rank and weight 4-byte aligned");
+    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_sample");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_prio<Backend>::sample(A, (long long)n_batches, (long long)min_live, alpha_beta, rows, act7, target, (long long *)seq, rank, weight,
+                                      pp->replay.block_threads, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_prio_sample: " + err);
+    return PVE_OK;
+}
+
+int pve_prio_update(pve_handle h, const pve_prio *pp, const int64_t *seq, const float *q, const float *target, int64_t n)
+{
+    PrioArgs A;
+    const int rc = prio_args(h, pp, "pve_prio_update", A);
+    if (rc != PVE_OK) return rc;
+    if (n < 0) return fail(PVE_ERR_INVALID, "pve_prio_update: n must be >= 0");
+    if (n > 0 && (!seq || !q)) return fail(PVE_ERR_INVALID, "pve_prio_update: null seq or q");
+    if (((uintptr_t)seq & 7) || ((uintptr_t)q & 3) || ((uintptr_t)target & 3))
+        return fail(PVE_ERR_INVALID, "pve_prio_update: seq must be 8-byte aligned, q and target 4-byte aligned");
+    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_update");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_prio<Backend>::update(A, (const long long *)seq, q, target, (long long)n, pp->replay.block_threads, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_prio_update: " + err);
     return PVE_OK;
 }
 

@@ -21,6 +21,7 @@
 #include "pve_critic.h"
 #include "pve_nstep.h"
 #include "pve_replay.h"
+#include "pve_prio.h"
 #include "pve_learn.h"
 
 using namespace pve;
@@ -1597,6 +1598,59 @@ struct Backend {
             if (check_launch(err) != 0) return -1;
         }
         return 0;
+    }
+    // pve_prio_reset: pseq = -1, pstate = 0
+    static int launch_prio_reset(const PrioArgs &A, int block_threads, void *stream, std::string &err)
+    {
+        const int block = block_threads > 0 ? block_threads : 256;
+        const long long want = (A.R.capacity + block - 1) / block;
+        hipLaunchKernelGGL(k_prio_reset, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(block), 0, (hipStream_t)stream, A);
+        return check_launch(err);
+    }
+    // pve_prio_rank: the keys, then four passes of histogram / scan / scatter over 8-bit digits, keys and payloads ping-pong
+    // between the two scratch halves; the last pass writes its payloads to `order`.  The grids cover the capacity: how many
+    // records are live is on the device only, a tile past them returns at once.
+    static int launch_prio_rank(const PrioArgs &A, int block_threads, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int block = block_threads > 0 ? block_threads : 256;
+        const long long want = (A.R.capacity + block - 1) / block;
+        const dim3 tiles((unsigned)prio_tiles(A.R.capacity));
+        hipLaunchKernelGGL(k_prio_keys, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(block), 0, s, A);
+        for (int pass = 0; pass < PRIO_PASSES; pass++) {
+            const int in = pass & 1, out = in ^ 1;
+            hipLaunchKernelGGL(k_prio_hist, tiles, dim3(block), 0, s, A, (const uint32_t *)A.keys[in], 8 * pass);
+            hipLaunchKernelGGL(k_prio_scan, dim3(PRIO_RADIX), dim3(block), 0, s, A, pass);
+            hipLaunchKernelGGL(k_prio_scatter, tiles, dim3(block), 0, s, A, (const uint32_t *)A.keys[in], (const int32_t *)A.vals[in],
+                               A.keys[out], pass == PRIO_PASSES - 1 ? A.order : A.vals[out], 8 * pass);
+        }
+        return check_launch(err);
+    }
+    // pve_prio_sample: the ranking, one workgroup per minibatch, then pdraws in a launch of its own
+    static int launch_prio_sample(const PrioArgs &A, long long n_batches, long long min_live, float alpha_beta, float *rows, float *act7,
+                                  float *target, long long *seq, int32_t *rank, float *weight, int block_threads, void *stream,
+                                  std::string &err)
+    {
+        if (launch_prio_rank(A, block_threads, stream, err) != 0) return -1;
+        hipStream_t s = (hipStream_t)stream;
+        const long long fit = (A.batch + 63) / 64 * 64;
+        const int block = block_threads > 0 ? block_threads : (int)(fit < 256 ? fit : 256);
+        hipLaunchKernelGGL(k_prio_sample, dim3((unsigned)n_batches), dim3(block), prio_sample_lds(block), s, A, min_live, alpha_beta, rows,
+                           act7, target, seq, rank, weight);
+        hipLaunchKernelGGL(k_prio_sample_commit, dim3(1), dim3(64), 0, s, A, min_live, n_batches);
+        return check_launch(err);
+    }
+    // pve_prio_update: stamp and zero, then the maximum -- two launches, so that no maximum meets a zeroing
+    static int launch_prio_update(const PrioArgs &A, const long long *seq, const float *q, const float *target, long long n,
+                                  int block_threads, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int block = block_threads > 0 ? block_threads : 256;
+        const long long want = (n + block - 1) / block;
+        const dim3 grid((unsigned)(want < 4096 ? (want > 0 ? want : 1) : 4096));
+        hipLaunchKernelGGL(k_prio_update_stamp, grid, dim3(block), 0, s, A, seq, n);
+        hipLaunchKernelGGL(k_prio_update_max, grid, dim3(block), 0, s, A, seq, q, target, n);
+        return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)
     {

@@ -11,6 +11,7 @@
 #include "pve_types.h"
 #include "pve_nstep.h"
 #include "pve_replay.h"
+#include "pve_prio.h"
 #include "pve_learn.h"
 
 namespace pve {

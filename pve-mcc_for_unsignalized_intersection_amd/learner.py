@@ -13,7 +13,8 @@ Per step, in the reference's order:
   2. actor_loss = -mean(Q(s, [actor(s), a7[1:]])) with the UPDATED critic, gradients with respect to the actor only, Adam on it;
   3. target = c1 * online + c2 * target for both networks, c1 = float32(1 - tau), c2 = float32(tau) (main.py:30).
 Adam is tf.train.AdamOptimizer's update (TF 1.x ApplyAdam) as the header writes it down; it is this library's definition.
-Not reproduced: td_error / update_priority (main.py:76-79, dead with rand_s=True) and the summaries."""
+Not part of the step: td_error / update_priority (main.py:76-79, dead with rand_s=True) are critic_q() on the sampled rows and
+PrioritizedReplayMemory.update_priority (replay.py).  Not reproduced: the summaries."""
 import ctypes as C
 
 import numpy as np

@@ -219,3 +219,270 @@ class ReplayMemory:
 
     def live(self):
         return min(self.count(), self.capacity)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The rank-based prioritised memory (csrc/pve_prio.h; reference rank_based.py `Experience`, which replay_buffer.py:13-18 builds in
+# every run and getBatch draws from with rand_s = False; main.py:76-79 td_error / update_priority).  PrioritizedReplayModel is the
+# host statement of the specification, PrioritizedReplayMemory the device memory (pve_prio_reset / _rank / _sample / _update).
+# Every integer part is bit-exact; the only floating-point arithmetic is the update's one subtraction and the importance weight.
+# Two stated departures from the reference: records of EQUAL priority are ordered by record number, newest first (the reference's
+# order among ties follows its heap layout), and an update that names a record overwritten since is ignored (the reference would
+# write onto the slot's new occupant).
+PRIO_PARTS = 32
+PRIO_NEW_BITS = 0x7F800000                   # +inf: a record that was never updated
+PRIO_TAG0, PRIO_TAG1 = 0x5052494F, 0x52414E4B      # "PRIO", "RANK": xored into the Philox key of the stratified draw
+PDRAWS, PLIVE, PPART, PIGNORED = 0, 1, 2, 3  # words of pstate
+_UNUSED_THRESHOLD = 1 << 62
+
+
+def strata_tables(size, batch_size, alpha=0.7, partition_num=PRIO_PARTS):
+    """(part_from int64 [32], ends int32 [32, batch_size + 1]): rank_based.py:40-80 and :159-163 restated with math.pow evaluated
+    once for all prefixes.  part_from[k] = the smallest L with floor(1.0 * L / size * partition_num) >= k + 1, by that float
+    expression; row k of ends is strata_ends of partition k + 1 (n = (k + 1) * floor(size / partition_num) ranks): math.fsum of the
+    prefix, np.cumsum(pdf / sum), the walk `while cdf[index] < step` with ends[0] = 0 and ends[batch_size] = n.  Rows and
+    thresholds past partition_num (< 32) are never reached: threshold 2^62, the last row repeated."""
+    import math
+    size, B, P = int(size), int(batch_size), int(partition_num)
+    if not 1 <= P <= PRIO_PARTS or size < P or B < 1:
+        raise ValueError("need 1 <= partition_num <= 32 <= ... <= size and batch_size >= 1")
+    psize = int(math.floor(1.0 * size / P))
+    if B > psize:
+        raise ValueError("batch_size %d exceeds the first partition's %d ranks" % (B, psize))
+    dist = np.floor(1.0 * np.arange(1, size + 1, dtype=np.float64) / size * P)           # dist_index of L = 1 .. size
+    part_from = np.full(PRIO_PARTS, _UNUSED_THRESHOLD, np.int64)
+    part_from[:P] = 1 + np.searchsorted(dist, np.arange(1, P + 1, dtype=np.float64), side="left")
+    powers = [math.pow(x, -alpha) for x in range(1, P * psize + 1)]
+    powers_np = np.array(powers, np.float64)
+    ends = np.zeros((PRIO_PARTS, B + 1), np.int32)
+    for k in range(P):
+        n = (k + 1) * psize
+        cdf = np.cumsum(powers_np[:n] / math.fsum(powers[:n]))
+        ends[k, B] = n
+        step, index = 1.0 / B, 1
+        for s in range(1, B):
+            index = max(index, int(np.searchsorted(cdf, step, side="left")))       # while cdf[index] < step: index += 1
+            if index >= n:
+                raise ValueError("strata walk ran past the partition (the reference raises IndexError)")
+            ends[k, s] = index
+            step += 1.0 / B
+        if part_from[k] < n:
+            raise ValueError("partition %d is reached with fewer live records than its %d ranks" % (k + 1, n))
+    ends[P:] = ends[P - 1]
+    return part_from, ends
+
+
+def prio_draw_ranks(seed, d, ends_row, L):
+    """ranks int64 [len(d), batch] of minibatches d from one table row (prio_draw_rank of the header)"""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    d = np.asarray(d, np.uint64).reshape(-1, 1)
+    row = np.asarray(ends_row, np.int64)
+    j = np.arange(len(row) - 1, dtype=np.uint64)[None, :]
+    u = philox4x32_10((j, np.uint64(0), d & np.uint64(0xFFFFFFFF), d >> np.uint64(32)),
+                      ((seed & 0xFFFFFFFF) ^ PRIO_TAG0, (seed >> 32) ^ PRIO_TAG1))[0]
+    lo, hi = np.minimum(row[:-1] + 1, row[1:]), np.maximum(row[:-1] + 1, row[1:])
+    r = lo[None, :] + ((u * (hi - lo + 1).astype(np.uint64)[None, :]) >> np.uint64(32)).astype(np.int64)
+    return np.clip(r, 1, int(L))
+
+
+def prio_weights(rank, alpha_beta):
+    """float64 (rank / rank_max)^alpha_beta per minibatch (rows of `rank`): rank_based.py:176-182 with the normaliser and
+    partition_max cancelled.  (The memories pass alpha_beta rounded to the float32 the device is given.)"""
+    rank = np.asarray(rank, np.float64)
+    return (rank / rank.max(axis=-1, keepdims=True)) ** float(alpha_beta)
+
+
+def prio_update_bits(q, target=None):
+    """uint32 bits of |q - target| in float32 (|q| without a target), NaN -> +inf"""
+    q = np.asarray(q, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = np.abs(q - np.asarray(target, np.float32)) if target is not None else np.abs(q)
+    return np.minimum(np.ascontiguousarray(p, np.float32).view(np.uint32), np.uint32(PRIO_NEW_BITS))
+
+
+class _PrioConfig:
+    """constructor arguments and tables shared by the model and the device class"""
+
+    def _configure(self, buffer_size, batch_size, seed, alpha, beta_zero, learn_start, steps, partition_num, error):
+        self.capacity, self.batch_size, self.seed = int(buffer_size), int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.alpha, self.beta_zero, self.learn_start, self.steps = float(alpha), float(beta_zero), int(learn_start), int(steps)
+        if not 1 <= self.capacity <= 0x7FFFFFFF or not 1 <= self.batch_size <= self.capacity:
+            raise error("need 1 <= batch_size <= buffer_size <= 2^31 - 1")
+        if self.steps == self.learn_start:
+            raise error("steps must differ from learn_start (rank_based.py:38 divides by their difference)")
+        try:
+            self.part_from, self.ends = strata_tables(self.capacity, self.batch_size, self.alpha, partition_num)
+        except ValueError as e:
+            raise error(str(e))
+        self.beta_grad = (1 - self.beta_zero) / (self.steps - self.learn_start)          # rank_based.py:38
+        self.min_live = max(self.learn_start, int(self.part_from[0]))
+
+    def beta_at(self, count):
+        """rank_based.py:176 with global_step = the adds ever made (replay_buffer.py:24)"""
+        return min(self.beta_zero + (int(count) - self.learn_start - 1) * self.beta_grad, 1)
+
+    def _alpha_beta(self, beta, error):
+        ab = np.float32(self.alpha * float(beta))
+        if not (np.isfinite(ab) and ab >= 0):
+            raise error("alpha * beta must be finite and >= 0")
+        return ab
+
+
+class PrioritizedReplayModel(ReplayModel, _PrioConfig):
+    """The prioritised memory on NumPy arrays: same methods and same results as PrioritizedReplayMemory.  capacity = buffer_size
+    (rank_based.py:82-99 cycles its index over 1 .. size; the uniform class keeps its buffer_size - 1)."""
+
+    def __init__(self, buffer_size=500000, batch_size=128, seed=0, alpha=0.7, beta_zero=0.5, learn_start=2000, steps=100000,
+                 partition_num=PRIO_PARTS):
+        self._configure(buffer_size, batch_size, seed, alpha, beta_zero, learn_start, steps, partition_num, ValueError)
+        self.store = np.zeros((self.capacity, RECORD), np.float32)
+        self.prio = np.zeros(self.capacity, np.uint32)
+        self.pseq = np.zeros(self.capacity, np.int64)
+        self.order = np.zeros(self.capacity, np.int32)
+        self.reset()
+
+    def reset(self):
+        ReplayModel.reset(self)
+        self.pseq[:] = -1
+        self.pstate = np.zeros(4, np.int64)
+
+    def keys(self):
+        """(keys uint32 [L], ages [L]) of the live records, newest first: the sort's input"""
+        L = self.live()
+        age = L - 1 - np.arange(L, dtype=np.int64)
+        w = self.written - L + age
+        s = w % self.capacity
+        bits = np.where(self.pseq[s] == w, self.prio[s], np.uint32(PRIO_NEW_BITS)).astype(np.uint32)
+        return ~bits, age
+
+    def rank(self):
+        """-> order int32 [L] (a view of self.order): the age index of the record of rank r + 1"""
+        L = self.live()
+        key, age = self.keys()
+        self.order[:L] = age[np.argsort(key, kind="stable")]
+        self.pstate[PLIVE], self.pstate[PPART] = L, int(np.count_nonzero(self.part_from <= L))
+        return self.order[:L]
+
+    def sample(self, n_batches=1, beta=None, check=True):
+        """-> (rows [n_batches, batch, 28], act7 [.., 7], target [..], seq int64 [..], rank int32 [..], weight float32 [..])"""
+        n, B = int(n_batches), self.batch_size
+        if n < 1:
+            raise ValueError("n_batches must be >= 1")
+        ab = self._alpha_beta(self.beta_at(self.count()) if beta is None else beta, ValueError)
+        order = self.rank()
+        L, part = self.live(), int(self.pstate[PPART])
+        if L < self.min_live or part == 0:
+            if check:
+                raise PveError("prioritised replay memory: %d live records, fewer than the %d it needs" % (L, self.min_live))
+            return (np.zeros((n, B, 28), np.float32), np.zeros((n, B, 7), np.float32), np.zeros((n, B), np.float32),
+                    np.full((n, B), -1, np.int64), np.zeros((n, B), np.int32), np.zeros((n, B), np.float32))
+        rank = prio_draw_ranks(self.seed, int(self.pstate[PDRAWS]) + np.arange(n, dtype=np.uint64), self.ends[part - 1], L)
+        seq = self.written - L + order[rank - 1].astype(np.int64)
+        rec = self.store[seq % self.capacity]
+        self.pstate[PDRAWS] += n
+        return (rec[..., :28].copy(), rec[..., 28:35].copy(), rec[..., 35].copy(), seq, rank.astype(np.int32),
+                prio_weights(rank, ab).astype(np.float32))
+
+    def update_priority(self, seq, q, target=None):
+        seq = np.asarray(seq, np.int64).ravel()
+        bits = prio_update_bits(np.asarray(q, np.float32).ravel(), None if target is None else np.asarray(target, np.float32).ravel())
+        if bits.shape != seq.shape:
+            raise ValueError("seq, q and target must have the same number of elements")
+        L = self.live()
+        ok = (seq >= self.written - L) & (seq < self.written)
+        self.pstate[PIGNORED] = int(np.count_nonzero(~ok))
+        s = seq[ok] % self.capacity
+        self.pseq[s], self.prio[s] = seq[ok], 0
+        np.maximum.at(self.prio, s, bits[ok])
+
+
+class PrioritizedReplayMemory(ReplayMemory, _PrioConfig):
+    """The prioritised memory on the device of `batch`: ReplayMemory's ring, add(), count() and live() with capacity =
+    buffer_size, plus the priority store, rank(), the stratified sample() and update_priority().  Nothing here synchronises but
+    sample(check=True), count() and live().  Priorities only matter for records that survive more than one sample / update round:
+    a trainer that uses this memory cuts its adds with nstep_transitions(max_records=...)."""
+
+    def __init__(self, batch, buffer_size=500000, batch_size=128, seed=0, alpha=0.7, beta_zero=0.5, learn_start=2000, steps=100000,
+                 partition_num=PRIO_PARTS, block_threads=0):
+        import torch
+        self._torch = torch
+        self.batch = batch
+        self._configure(buffer_size, batch_size, seed, alpha, beta_zero, learn_start, steps, partition_num, PveError)
+        scratch_bytes = int(batch.lib.pve_prio_scratch_bytes(self.capacity))
+        self._ends_host = np.ascontiguousarray(self.ends, np.int32)
+        self._part_from = np.ascontiguousarray(self.part_from, np.int64)
+        with batch._own_stream():
+            dev = batch.device
+            self.store = torch.zeros(self.capacity, RECORD, dtype=torch.float32, device=dev)
+            self.state = torch.zeros(_capi.REPLAY_STATE_WORDS, dtype=torch.int64, device=dev)
+            self.prio = torch.zeros(self.capacity, dtype=torch.int32, device=dev)          # (uint32 bit patterns)
+            self.pseq = torch.full((self.capacity,), -1, dtype=torch.int64, device=dev)
+            self.order = torch.zeros(self.capacity, dtype=torch.int32, device=dev)
+            self.pstate = torch.zeros(_capi.PRIO_STATE_WORDS, dtype=torch.int64, device=dev)
+            self.scratch = torch.empty(scratch_bytes // 4, dtype=torch.int32, device=dev)
+            self.ends_dev = torch.as_tensor(self._ends_host).to(dev)
+        self._pp = _capi.PvePrio()
+        self._rp = self._pp.replay                           # (ReplayMemory's calls go through the embedded struct)
+        self._rp.capacity, self._rp.store, self._rp.state = self.capacity, self.store.data_ptr(), self.state.data_ptr()
+        self._rp.seed, self._rp.block_threads = self.seed, int(block_threads)
+        p = self._pp
+        p.prio, p.pseq, p.order, p.pstate = self.prio.data_ptr(), self.pseq.data_ptr(), self.order.data_ptr(), self.pstate.data_ptr()
+        p.scratch, p.scratch_bytes, p.ends, p.batch = self.scratch.data_ptr(), scratch_bytes, self.ends_dev.data_ptr(), self.batch_size
+        p.ends_host, p.part_from = self._ends_host.ctypes.data, self._part_from.ctypes.data
+
+    def _pcall(self, fn, what, *args):
+        b = self.batch
+        b._bind_stream()
+        check(b.lib, fn(b._h, C.byref(self._pp), *args), what)
+
+    def reset(self):
+        with self.batch._own_stream():
+            self._call(self.batch.lib.pve_replay_reset, "pve_replay_reset")
+            self._pcall(self.batch.lib.pve_prio_reset, "pve_prio_reset")
+
+    def rank(self):
+        """Rank the live records -> order (int32 device tensor [capacity]; its first live() entries are the age indices by rank)"""
+        with self.batch._own_stream():
+            self._pcall(self.batch.lib.pve_prio_rank, "pve_prio_rank")
+        return self.order
+
+    def sample(self, n_batches=1, beta=None, check=True):
+        """Rank, then draw n_batches stratified minibatches -> (rows, act7, target, seq, rank int32 [n_batches, batch_size],
+        weight float32 [..]).  beta=None: beta_at(count()), which synchronises; pass beta to stay asynchronous.  check as in
+        ReplayMemory.sample: True reads one status word and raises PveError when the memory is short (fewer live records than
+        max(learn_start, part_from[0])), False never synchronises and a short memory gives seq = -1 and zeros."""
+        torch = self._torch
+        b, n, B = self.batch, int(n_batches), self.batch_size
+        if n < 1:
+            raise PveError("PrioritizedReplayMemory.sample: n_batches must be >= 1")
+        ab = self._alpha_beta(self.beta_at(self.count()) if beta is None else beta, PveError)
+        with b._own_stream():
+            rows = torch.empty(n, B, 28, dtype=torch.float32, device=b.device)
+            act7 = torch.empty(n, B, 7, dtype=torch.float32, device=b.device)
+            target = torch.empty(n, B, dtype=torch.float32, device=b.device)
+            seq = torch.empty(n, B, dtype=torch.int64, device=b.device)
+            rank = torch.empty(n, B, dtype=torch.int32, device=b.device)
+            weight = torch.empty(n, B, dtype=torch.float32, device=b.device)
+            self._pcall(b.lib.pve_prio_sample, "pve_prio_sample", n, self.min_live, C.c_float(float(ab)), *(C.c_void_p(t.data_ptr())
+                        for t in (rows, act7, target, seq, rank, weight)))
+            if check:
+                L = int(self.pstate[PLIVE].item())
+                if L < self.min_live:
+                    raise PveError("prioritised replay memory: %d live records, fewer than the %d it needs" % (L, self.min_live))
+        return rows, act7, target, seq, rank, weight
+
+    def update_priority(self, seq, q, target=None):
+        """Store |q - target| (|q| without a target) as the priority of the records `seq` names: int64 / float32 device tensors
+        of equal element counts, e.g. sample()'s seq and target and critic_q(rows, act7)."""
+        torch = self._torch
+        b = self.batch
+        want = (("seq", seq, torch.int64), ("q", q, torch.float32)) + ((("target", target, torch.float32),) if target is not None else ())
+        for name, t, dt in want:
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self.store.device or t.numel() != seq.numel():
+                raise PveError("PrioritizedReplayMemory.update_priority: %s must be a %s tensor on %s with seq's element count"
+                               % (name, dt, self.store.device))
+        with b._own_stream():
+            seq, q = seq.contiguous(), q.contiguous()
+            target = target.contiguous() if target is not None else None
+            self._pcall(b.lib.pve_prio_update, "pve_prio_update", C.c_void_p(seq.data_ptr()), C.c_void_p(q.data_ptr()),
+                        C.c_void_p(target.data_ptr() if target is not None else 0), int(seq.numel()))
