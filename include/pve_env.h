@@ -552,6 +552,46 @@ int pve_prio_sample(pve_handle h, const pve_prio *pp, int64_t n_batches, int64_t
 int pve_prio_update(pve_handle h, const pve_prio *pp, const int64_t *seq, const float *q, const float *target /* or NULL */,
                     int64_t n);
 
+/* ARRIVAL STREAMS generated on the device: the per-episode input that the reference reads with scipy.io.loadmat (main.py:228-229,
+ * :388-389 `arvTimeNewVeh`) and, for the 8-lane layout, the random.randint(0, 1) it draws per arriving vehicle (ref :381, :390),
+ * written in place on the handle's stream.  Additive within ABI 9: one new symbol (declared in include/pve_env_arrivals.h) and one
+ * new struct, nothing existing changes, PVE_ABI_VERSION stays 9; a binding detects an older library by the missing symbol.  The specification is csrc/pve_arrivals.h
+ * (host + device), restated in NumPy as pve_mcc_amd.arrivals.device_arrivals / device_intentions; every implementation is
+ * bit-equal to it.
+ * arrivals: float64 [n_envs][rows][lane_num] (n_envs and lane_num are the handle's), the layout pve_set_arrivals takes with
+ * env_stride_rows = rows.  With env_global = env index + env_offset, row r < rows - 1 and lane l:
+ *   w = output word (r & 3) of Philox4x32-10, counter = ((r >> 2) | (l << 28), epoch, env_global low word, env_global high word),
+ *   key = (seed low word ^ 0x41525256, seed high word ^ 0x54494D45)  -- apart from the exploration noise (raw seed) and the
+ *   prioritised draw (^ 0x5052494F / 0x52414E4B) under one seed;
+ *   x = -ln((2 w + 1) 2^-33) in the exact binary64 arithmetic pve_arrivals.h writes down (x in [1.16e-10, 22.874], never 0);
+ *   d = mean * x, raised to min_gap_s if below;  t[0] = d[0], t[r] = t[r-1] + d[r]: float64 additions in ascending r.
+ * mean = mean_s seconds (3600 / rate in veh/h/lane), or mean_env[env] when mean_env is not NULL (DEVICE memory: its entries must
+ * be finite and > 0, which the call cannot check).  Row rows - 1 is +inf in every lane.  A chain is a pure function of (seed,
+ * epoch, env_global, l, r): fewer rows give a prefix, a batch cut into pieces with matching env_offset gives the same streams.
+ * With min_gap_s = 1, t[r] >= r + 1 exactly, so rows - 1 seconds of run are always covered.
+ * intentions (lane_num = 8 only, or NULL): int32 [n_envs][rows][8], entry (e, r, l) = bit (r & 31) of output word ((r >> 5) & 3)
+ * of Philox4x32-10 with counter = ((r >> 7) | (l << 28), epoch, env_global low word, env_global high word), key = (seed low word
+ * ^ 0x494E5445, seed high word ^ 0x4E54494F); every row, the layout pve_set_intentions takes with env_stride_rows = rows.
+ * covered (or NULL): float64 [n_envs], covered[e] = min over lanes of t[e][rows - 2][l]: how far the stream is sure to reach.
+ * The call is asynchronous on the handle's stream and never synchronises.  It does NOT install the stream: pve_set_arrivals /
+ * pve_set_intentions (which only record pointers) do, before or after.  block_threads: 0 = default; else a multiple of 64 up to
+ * 1024 (diagnostics: same results).
+ * Errors (PVE_ERR_INVALID): null h / g / arrivals; env_offset < 0; rows outside 2 .. 2^28; mean_env NULL and mean_s not finite or
+ * <= 0; min_gap_s negative or not finite; block_threads; intentions with lane_num != 8; arrivals or intentions not 16-byte
+ * aligned, covered or mean_env not 8-byte aligned; a backend without the kernels. */
+typedef struct pve_arrival_gen {
+    uint64_t seed;
+    int64_t  env_offset;      /* >= 0 */
+    uint32_t epoch;
+    int32_t  rows;            /* 2 .. 2^28 */
+    double   mean_s;          /* finite, > 0; used when mean_env is NULL */
+    const double *mean_env;   /* DEVICE [n_envs] or NULL */
+    double   min_gap_s;       /* finite, >= 0 */
+    int32_t  block_threads;   /* 0 = default */
+} pve_arrival_gen;
+/* The prototype of the call is in include/pve_env_arrivals.h, an extension header of its own: this file's list of entry points
+ * stays the 44 that bindings and checks of ABI 9 count; entry points added later come in such headers. */
+
 /* MANY TICKS, host out of the loop: the reference's episode loop `for i in range(1000): ... step / scene_update /
  * delete_vehicle` (main.py:397-441) with the action source on the device, as ONE call.  Tick k of the call is exactly
  * pve_step_all() with

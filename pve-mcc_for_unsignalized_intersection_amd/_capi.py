@@ -84,6 +84,11 @@ class PvePrio(C.Structure):
                 ("part_from", C.c_void_p), ("batch", C.c_int64)]
 
 
+class PveArrivalGen(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("env_offset", C.c_int64), ("epoch", C.c_uint32), ("rows", C.c_int32), ("mean_s", C.c_double),
+                ("mean_env", C.c_void_p), ("min_gap_s", C.c_double), ("block_threads", C.c_int32)]
+
+
 class PveLearner(C.Structure):
     _fields_ = [("params", C.c_void_p), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
                 ("beta2", C.c_float), ("epsilon", C.c_float), ("tau", C.c_float), ("flags", C.c_int32), ("block_threads", C.c_int32)]
@@ -113,6 +118,8 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather",
            "pve_replay_reset", "pve_replay_append", "pve_replay_sample", "pve_learner_init", "pve_learner_step",
            "pve_learner_step_wide", "pve_prio_scratch_bytes", "pve_prio_reset", "pve_prio_rank", "pve_prio_sample", "pve_prio_update")
+# entry points declared in extension headers (include/pve_env_arrivals.h), added within ABI 9 behind include/pve_env.h's 44
+EXPORTS_EXT = ("pve_generate_arrivals",)
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -162,9 +169,10 @@ def _declare(L):
     L.pve_prio_rank.argtypes = [vp, C.POINTER(PvePrio)]
     L.pve_prio_sample.argtypes = [vp, C.POINTER(PvePrio), C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp]
     L.pve_prio_update.argtypes = [vp, C.POINTER(PvePrio), vp, vp, vp, C.c_int64]
+    L.pve_generate_arrivals.argtypes = [vp, C.POINTER(PveArrivalGen), vp, vp, vp]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
-    for name in EXPORTS:
+    for name in EXPORTS + EXPORTS_EXT:
         if name not in ("pve_last_error", "pve_workspace_bytes", "pve_default_config", "pve_prio_scratch_bytes"):
             getattr(L, name).restype = C.c_int
     L.pve_default_config.restype = None
@@ -184,7 +192,7 @@ def load_library(path=None):
         raise PveError("%s not found: build the HIP library first (python -c 'import __graft_entry__ as g; "
                        "g.build()' or make -C %s/csrc). There is no CPU fallback." % (p, _HERE))
     dll = C.CDLL(p)
-    missing = [n for n in EXPORTS if not hasattr(dll, n)]
+    missing = [n for n in EXPORTS + EXPORTS_EXT if not hasattr(dll, n)]
     if missing:       # (the target-network entry points were added within ABI 9: an older build lacks the symbols)
         raise PveError("%s is an older build: it lacks %s (rebuild it)" % (p, ", ".join(missing)))
     L = _declare(dll)

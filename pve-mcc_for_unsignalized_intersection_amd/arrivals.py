@@ -27,6 +27,98 @@ def synthetic_intentions(n_envs, rows, seed=20250213, lane_num=8):
     return out
 
 
+# ---------------------------------------------------------------------------------------------
+# NumPy restatement of csrc/pve_arrivals.h, operation for operation: the streams pve_generate_arrivals
+# (BatchedIntersections.generate_arrivals) writes on the device, bit for bit.
+ARR_KEY = (0x41525256, 0x54494D45)
+INT_KEY = (0x494E5445, 0x4E54494F)
+
+
+def exp_from_words(w):
+    """x = -ln((2 w + 1) 2^-33) of 32-bit words as float64: pve_arrivals.h's arrival_exp (the logarithm of noise_gauss's radius)."""
+    from .noise import _LN2, _LOG_C, _MASK32, _SQRT_HALF
+    w = np.asarray(w, np.uint64) & _MASK32
+    m = (w * np.uint64(2) + np.uint64(1)).astype(np.float64)            # exact: < 2^33
+    f, e = np.frexp(m)                                                  # exact: m = f 2^e, f in [1/2, 1)
+    e = e.astype(np.int64)
+    low = f < _SQRT_HALF
+    f = np.where(low, f * 2.0, f)
+    e = np.where(low, e - 1, e)
+    s = (f - 1.0) / (f + 1.0)
+    s2 = s * s
+    L = np.full_like(s, _LOG_C[0])
+    for c in _LOG_C[1:]:
+        L = L * s2 + c
+    return (33 - e).astype(np.float64) * _LN2 - 2.0 * (s * L)
+
+
+def _env_words(n_envs, env_offset):
+    env = (np.arange(n_envs, dtype=np.int64) + int(env_offset)).astype(np.uint64)
+    return env & np.uint64(0xFFFFFFFF), env >> np.uint64(32)
+
+
+def _keys(seed, tweak):
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return (seed & 0xFFFFFFFF) ^ tweak[0], (seed >> 32) ^ tweak[1]
+
+
+def device_mean(rate, n_envs):
+    """mean gap in seconds, float64 [n_envs]: 3600 / rate with rate in veh/h/lane, a scalar or one per environment"""
+    r = np.asarray(rate, np.float64)
+    if r.ndim not in (0, 1) or (r.ndim == 1 and r.shape[0] != n_envs):
+        raise ValueError("rate must be a scalar or [n_envs]")
+    return np.broadcast_to(3600.0 / r, (n_envs,)).astype(np.float64)
+
+
+def default_rows(rate, horizon_s):
+    """The rows synthetic_arrivals allots to horizon_s seconds -- 64 + 2 ceil(horizon / mean) -- at the largest rate"""
+    mean = 3600.0 / float(np.max(np.asarray(rate, np.float64)))
+    return 64 + int(np.ceil(horizon_s / mean)) * 2
+
+
+def arrival_words(n_envs, rows, lane_num, seed=0, epoch=0, env_offset=0):
+    """uint64 [n_envs, rows - 1, lane_num]: the 32-bit Philox word behind every gap of device_arrivals"""
+    from .noise import philox4x32_10
+    lo, hi = _env_words(n_envs, env_offset)
+    quads = (rows - 1 + 3) // 4
+    c0 = np.arange(quads, dtype=np.uint64)[None, :, None] | (np.arange(lane_num, dtype=np.uint64)[None, None, :] << np.uint64(28))
+    words = philox4x32_10((c0, np.uint64(int(epoch) & 0xFFFFFFFF), lo[:, None, None], hi[:, None, None]), _keys(seed, ARR_KEY))
+    return np.stack(words, axis=2).reshape(n_envs, quads * 4, lane_num)[:, :rows - 1]    # row 4 q + k = word k of quad q
+
+
+def device_arrivals(n_envs, rows, lane_num, rate, seed=0, epoch=0, env_offset=0, min_gap=1.0):
+    """float64 [n_envs, rows, lane_num]: the stream pve_generate_arrivals writes (csrc/pve_arrivals.h).  Row r < rows - 1 of
+    chain (env, lane) is the running float64 sum, in ascending r, of max(min_gap, mean * x) with x the exponential deviate of
+    Philox word r & 3 at counter ((r >> 2) | (lane << 28), epoch, env_global low, high); row rows - 1 is +inf.
+    np.cumsum along the rows adds sequentially in that order (tests/test_arrivals_device.py asserts it)."""
+    if rows < 2:
+        raise ValueError("rows must be >= 2")
+    mean = device_mean(rate, n_envs)
+    d = mean[:, None, None] * exp_from_words(arrival_words(n_envs, rows, lane_num, seed, epoch, env_offset))
+    d = np.where(d < float(min_gap), float(min_gap), d)
+    out = np.full((n_envs, rows, lane_num), np.inf, dtype=np.float64)
+    out[:, :rows - 1] = np.cumsum(d, axis=1)
+    return out
+
+
+def device_intentions(n_envs, rows, seed=0, epoch=0, env_offset=0, lane_num=8):
+    """int32 [n_envs, rows, lane_num] of 0/1: the intention draws pve_generate_arrivals writes for the 8-lane layout: entry (e, r, l)
+    is bit r & 31 of Philox word (r >> 5) & 3 at counter ((r >> 7) | (l << 28), epoch, env_global low, high)."""
+    from .noise import philox4x32_10
+    lo, hi = _env_words(n_envs, env_offset)
+    chunks = (rows + 127) // 128
+    c0 = np.arange(chunks, dtype=np.uint64)[None, :, None] | (np.arange(lane_num, dtype=np.uint64)[None, None, :] << np.uint64(28))
+    words = philox4x32_10((c0, np.uint64(int(epoch) & 0xFFFFFFFF), lo[:, None, None], hi[:, None, None]), _keys(seed, INT_KEY))
+    w = np.stack(words, axis=2)                                                          # [n_envs, chunks, 4, lane_num]
+    bits = (w[:, :, :, None, :] >> np.arange(32, dtype=np.uint64)[None, None, None, :, None]) & np.uint64(1)
+    return bits.reshape(n_envs, chunks * 128, lane_num)[:, :rows].astype(np.int32)
+
+
+def device_covered(arrivals):
+    """float64 [n_envs]: min over lanes of the last finite row, what pve_generate_arrivals reports as `covered`"""
+    return np.asarray(arrivals)[:, -2, :].min(axis=1)
+
+
 def pad_stream(arr, extra_rows=1):
     """Replace the zero padding at the tail of a shipped stream by +inf so that an
     exhausted lane simply stops spawning (the reference would spawn every tick, ref :379)."""

@@ -36,7 +36,8 @@ class BatchedIntersections:
               arrival stream or a slow policy wants 256.
 
     arrivals: float64 array/tensor [rows, lane_num] (shared by all envs) or [n_envs, rows, lane_num]; the
-              reference's `arrive_time` matrix (main.py:388-389). Pad with +inf.
+              reference's `arrive_time` matrix (main.py:388-389). Pad with +inf.  None: no stream yet --
+              generate_arrivals() produces it on the device (or set_arrivals() installs one) before reset().
     outputs:  names of per-tick output buffers to allocate (see include/pve_env.h `pve_outputs`).
     intentions: lane_num = 8 only -- int array [rows, 8] / [n_envs, rows, 8] of 0/1: the reference's
               random.randint(0, 1) draws (ref :390) as an input stream (None = zeros).
@@ -85,7 +86,9 @@ class BatchedIntersections:
                                             C.c_void_p(self.workspace.data_ptr()), sptr, C.byref(h)),
               "pve_create")
         self._h = h
-        self.set_arrivals(arrivals)
+        self.arrivals = None
+        if arrivals is not None:              # (None: generate_arrivals() will produce the stream on the device)
+            self.set_arrivals(arrivals)
         self.intentions = None
         if intentions is not None:
             self.set_intentions(intentions)
@@ -164,6 +167,62 @@ class BatchedIntersections:
         check(self.lib, self.lib.pve_set_intentions(self._h, C.c_void_p(self.intentions.data_ptr()), rows, stride_rows),
               "pve_set_intentions")
         self._is_reset = False
+
+    def generate_arrivals(self, rate, horizon_s=None, rows=None, seed=0, epoch=0, env_offset=0, min_gap=1.0, covered=False):
+        """The next episode's arrival stream, generated on the device and installed (pve_generate_arrivals; replaces the
+        loadmat of main.py:228-229 / :388-389 and, for lane_num = 8, the intention draws of ref :381, :390): self.arrivals
+        [n_envs, rows, lane_num] = arrivals.device_arrivals(...) bit for bit, for lane_num = 8 also self.intentions
+        [n_envs, rows, 8] = arrivals.device_intentions(...).  No host work and no synchronisation: generate -> reset ->
+        step_many can be enqueued back to back, and regenerating into the same buffers is ordered by the stream.
+        rate: veh/h/lane, a scalar or one value per environment (array, or a float64 device tensor).  rows: given, or
+        arrivals.default_rows(rate, horizon_s) (a per-environment rate on the device needs `rows`).  epoch: a new stream per episode
+        under one seed.  env_offset: global index of this batch's first environment when the batch is a piece of a larger one.
+        The buffers are allocated on the batch's stream and reused while the shape stays (a stream passed to the constructor or
+        to set_arrivals is never written to).  covered=True returns the float64 [n_envs] tensor of times every lane of an
+        environment is sure to reach (else None); read it when convenient.  Needs reset() afterwards."""
+        from .arrivals import default_rows, device_mean
+        E, ln = self.n_envs, self.lane_num
+        on_device = torch.is_tensor(rate) and rate.device.type == self.device.type == "cuda"
+        if rows is None:
+            if horizon_s is None or on_device:
+                raise PveError("generate_arrivals: pass rows or horizon_s (a rate tensor on the device needs rows)")
+            rows = default_rows(rate.cpu().numpy() if torch.is_tensor(rate) else rate, horizon_s)
+        rows = int(rows)
+        per_env = on_device or np.ndim(rate.cpu().numpy() if torch.is_tensor(rate) else rate) > 0
+        g = _capi.PveArrivalGen(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, env_offset=int(env_offset), epoch=int(epoch) & 0xFFFFFFFF, rows=rows,
+                                mean_s=1.0, mean_env=None, min_gap_s=float(min_gap), block_threads=0)
+        self._bind_stream()
+        with self._own_stream():
+            mean = None
+            if on_device:
+                if rate.dtype != torch.float64 or tuple(rate.shape) != (E,):
+                    raise PveError("generate_arrivals: a rate tensor must be float64 [n_envs]")
+                mean = 3600.0 / rate
+            elif per_env:
+                mean = torch.as_tensor(device_mean(rate.cpu().numpy() if torch.is_tensor(rate) else rate, E)).to(self.device)
+            else:
+                g.mean_s = 3600.0 / float(rate)
+            if mean is not None:
+                g.mean_env = mean.data_ptr()
+            buf = self.__dict__.setdefault("_gen_buffers", {})
+            if buf.get("arrivals") is None or tuple(buf["arrivals"].shape) != (E, rows, ln):
+                buf["arrivals"] = torch.empty(E, rows, ln, dtype=torch.float64, device=self.device)
+                buf["intentions"] = torch.empty(E, rows, ln, dtype=torch.int32, device=self.device) if ln == 8 else None
+            arr, ch = buf["arrivals"], buf["intentions"]
+            cov = torch.empty(E, dtype=torch.float64, device=self.device) if covered else None
+            check(self.lib, self.lib.pve_generate_arrivals(self._h, C.byref(g), C.c_void_p(arr.data_ptr()),
+                                                           C.c_void_p(ch.data_ptr()) if ch is not None else None,
+                                                           C.c_void_p(cov.data_ptr()) if cov is not None else None),
+                  "pve_generate_arrivals")
+            if mean is not None and self._stream_obj is not None and mean.is_cuda:
+                mean.record_stream(self._stream_obj)
+        self.arrivals = arr
+        check(self.lib, self.lib.pve_set_arrivals(self._h, C.c_void_p(arr.data_ptr()), rows, rows), "pve_set_arrivals")
+        if ch is not None:
+            self.intentions = ch
+            check(self.lib, self.lib.pve_set_intentions(self._h, C.c_void_p(ch.data_ptr()), rows, rows), "pve_set_intentions")
+        self._is_reset = False
+        return cov
 
     def state_field(self, name):
         """Zero-copy [n_envs, capacity] view of a persistent per-slot field (see pve_state_field)."""
@@ -837,6 +896,23 @@ class PipelinedIntersections:
         the pieces draw the noise one batch of n_envs environments draws."""
         for k, sub in enumerate(self.subs):
             sub.set_exploration(sigma, seed, env_offset=self.bounds[k])
+
+    def generate_arrivals(self, rate, horizon_s=None, rows=None, seed=0, epoch=0, env_offset=0, min_gap=1.0, covered=False):
+        """BatchedIntersections.generate_arrivals for every sub-batch on its own stream, each with the global index of its
+        first environment (+ env_offset): the pieces generate the streams one batch of n_envs environments generates.
+        rate: a scalar or [n_envs], cut at `bounds`.  Returns the list of per-sub-batch `covered` tensors, or None."""
+        from .arrivals import default_rows
+        host_rate = rate.cpu().numpy() if torch.is_tensor(rate) and rate.device.type != "cuda" else rate
+        if rows is None and horizon_s is not None and not torch.is_tensor(host_rate):
+            rows = default_rows(host_rate, horizon_s)             # (one row count for all pieces: the largest rate of the batch)
+        per_env = torch.is_tensor(host_rate) or np.ndim(host_rate) > 0
+        cov = []
+        for k, sub in enumerate(self.subs):
+            with self._on(k):
+                cov.append(sub.generate_arrivals(host_rate[self.bounds[k]:self.bounds[k + 1]] if per_env else host_rate, horizon_s=horizon_s,
+                                                 rows=rows, seed=seed, epoch=epoch, env_offset=int(env_offset) + self.bounds[k],
+                                                 min_gap=min_gap, covered=covered))
+        return cov if covered else None
 
     def step_with_actor(self):
         return [sub.step_with_actor() for sub in self.subs]

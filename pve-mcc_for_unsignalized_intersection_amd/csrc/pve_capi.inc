@@ -56,6 +56,8 @@
 //     static int   launch_prio_update(const pve::PrioArgs &, const long long *seq, const float *q, const float *target, long long n,
 //                                     int block_threads, void *stream, std::string &err);
 //                                                // optional, all four or none: pve_prio_reset / _rank / _sample / _update (csrc/pve_prio.h)
+//     static int   launch_generate_arrivals(const pve::ArrivalArgs &, int block_threads, void *stream, std::string &err);
+//                                                // optional: pve_generate_arrivals (csrc/pve_arrivals.h)
 //     static int   launch_learner_init(float *params, const float *actor, const float *critic, const float *target_actor,
 //                                      const float *target_critic, float beta1, float beta2, void *stream, std::string &err);
 //     static int   launch_learner_step(const pve::LearnCtx &, int block_threads, void *stream, std::string &err);
@@ -291,6 +293,16 @@ template <class B> struct backend_prio<B, decltype((void)&B::launch_prio_sample)
     }
     static int update(const PrioArgs &A, const long long *seq, const float *q, const float *target, long long n, int block, void *stream,
                       std::string &err) { return B::launch_prio_update(A, seq, q, target, n, block, stream, err); }
+};
+// The arrival generator (pve_generate_arrivals) needs the kernels of pve_arrivals.h: Backend::launch_generate_arrivals.  A backend
+// without it exports the entry point all the same; it validates its arguments and then refuses with PVE_ERR_INVALID.
+template <class B, class = void> struct backend_arrivals {
+    static constexpr bool value = false;
+    static int generate(const ArrivalArgs &, int, void *, std::string &) { return -1; }
+};
+template <class B> struct backend_arrivals<B, decltype((void)&B::launch_generate_arrivals)> {
+    static constexpr bool value = true;
+    static int generate(const ArrivalArgs &A, int block, void *stream, std::string &err) { return B::launch_generate_arrivals(A, block, stream, err); }
 };
 // The learner step (pve_learner_init / pve_learner_step) needs the kernels behind Backend::launch_learner_init /
 // launch_learner_step (detected by the second).  A backend without them exports the entry points all the same; they validate
@@ -949,6 +961,35 @@ int pve_learner_step_wide(pve_handle h, const pve_learner *lrn, const float *row
     std::string err;
     if (backend_learner_wide<Backend>::step(C, work, (int)groups, lrn->block_threads, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_learner_step_wide: " + err);
+    return PVE_OK;
+}
+
+// The arrival stream of an episode, generated in place (replaces the loadmat of main.py:228-229 / :388-389 and, for the 8-lane
+// layout, the intention draws of ref :381, :390).  It does not install the stream: pve_set_arrivals / pve_set_intentions do.
+int pve_generate_arrivals(pve_handle h, const pve_arrival_gen *g, double *arrivals, int32_t *intentions, double *covered)
+{
+    if (!h || !g || !arrivals) return fail(PVE_ERR_INVALID, "pve_generate_arrivals: null handle, descriptor or arrivals");
+    if (g->env_offset < 0) return fail(PVE_ERR_INVALID, "pve_generate_arrivals: env_offset must be >= 0");
+    if (g->rows < 2 || g->rows > ARR_MAX_ROWS) return fail(PVE_ERR_INVALID, "pve_generate_arrivals: rows must be 2 .. 2^28");
+    if (!g->mean_env && (!(g->mean_s > 0) || g->mean_s > 1.7976931348623157e308))
+        return fail(PVE_ERR_INVALID, "pve_generate_arrivals: mean_s must be finite and > 0");
+    if (!(g->min_gap_s >= 0) || g->min_gap_s > 1.7976931348623157e308)
+        return fail(PVE_ERR_INVALID, "pve_generate_arrivals: min_gap_s must be finite and >= 0");
+    if (g->block_threads < 0 || g->block_threads > 1024 || g->block_threads % 64)
+        return fail(PVE_ERR_INVALID, "pve_generate_arrivals: block_threads must be 0 or a multiple of 64 up to 1024");
+    if (intentions && h->lane_num != 8)
+        return fail(PVE_ERR_INVALID, "pve_generate_arrivals: only lane_num = 8 draws intentions (ref :389-390)");
+    if (((uintptr_t)arrivals & 15) || ((uintptr_t)intentions & 15) || ((uintptr_t)covered & 7) || ((uintptr_t)g->mean_env & 7))
+        return fail(PVE_ERR_INVALID, "pve_generate_arrivals: arrivals and intentions must be 16-byte aligned, covered and mean_env 8-byte");
+    if (!backend_arrivals<Backend>::value) return fail(PVE_ERR_INVALID, "pve_generate_arrivals: this backend has no arrival generator kernels");
+    ArrivalArgs A;
+    A.seed = g->seed; A.env_offset = (long long)g->env_offset; A.epoch = g->epoch; A.rows = g->rows; A.n_envs = h->n_envs;
+    A.lane_num = h->lane_num; A.mean = g->mean_s; A.mean_env = g->mean_env; A.min_gap = g->min_gap_s; A.arrivals = arrivals;
+    A.intentions = intentions; A.covered = covered;
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_arrivals<Backend>::generate(A, g->block_threads, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_generate_arrivals: " + err);
     return PVE_OK;
 }
 

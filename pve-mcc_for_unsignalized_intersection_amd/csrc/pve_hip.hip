@@ -15,6 +15,7 @@
 #include <new>
 
 #include "pve_host.h"
+#include "../../include/pve_env_arrivals.h"      // (holds the definition in this translation unit to the public prototype)
 #include "pve_tick_core.h"
 #include "pve_tick_geo.h"
 #include "pve_actor.h"
@@ -22,6 +23,7 @@
 #include "pve_nstep.h"
 #include "pve_replay.h"
 #include "pve_prio.h"
+#include "pve_arrivals.h"
 #include "pve_learn.h"
 
 using namespace pve;
@@ -1650,6 +1652,18 @@ struct Backend {
         const dim3 grid((unsigned)(want < 4096 ? (want > 0 ? want : 1) : 4096));
         hipLaunchKernelGGL(k_prio_update_stamp, grid, dim3(block), 0, s, A, seq, n);
         hipLaunchKernelGGL(k_prio_update_max, grid, dim3(block), 0, s, A, seq, q, target, n);
+        return check_launch(err);
+    }
+    // pve_generate_arrivals: one workgroup per ARR_GROUP environments; the intentions in a launch of their own
+    static int launch_generate_arrivals(const ArrivalArgs &A, int block_threads, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int block = block_threads > 0 ? block_threads : 256;
+        hipLaunchKernelGGL(k_gen_arrivals, dim3((unsigned)((A.n_envs + ARR_GROUP - 1) / ARR_GROUP)), dim3(block), 0, s, A);
+        if (A.intentions) {
+            const long long items = (((long long)A.rows + ARR_INT_ROWS - 1) / ARR_INT_ROWS) * A.n_envs;
+            hipLaunchKernelGGL(k_gen_intentions, dim3((unsigned)(items < (1 << 20) ? items : (1 << 20))), dim3(block), 0, s, A);
+        }
         return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)

@@ -12,6 +12,7 @@
 #include "pve_nstep.h"
 #include "pve_replay.h"
 #include "pve_prio.h"
+#include "pve_arrivals.h"
 #include "pve_learn.h"
 
 namespace pve {

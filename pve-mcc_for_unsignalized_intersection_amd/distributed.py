@@ -21,6 +21,21 @@ def set_shard_exploration(batch, sigma, seed, n_total, rank, world):
     batch.set_exploration(sigma, seed, env_offset=shard_range(n_total, rank, world)[0])
 
 
+def generate_shard_arrivals(batch, rate, n_total, rank, world, horizon_s=None, rows=None, seed=0, epoch=0, min_gap=1.0, covered=False):
+    """Arrival streams (BatchedIntersections.generate_arrivals) for the shard `rank` holds of n_total environments: its
+    env_offset is the shard's first global env index, so the ranks together generate what one batch of n_total envs generates.
+    rate: a scalar, or [n_total] (every rank passes the whole vector: the shard's piece is cut here and the row count follows
+    the largest rate of all, so every rank allots the same rows)."""
+    import numpy as np
+    from .arrivals import default_rows
+    lo, hi = shard_range(n_total, rank, world)
+    r = np.asarray(rate.cpu().numpy() if torch.is_tensor(rate) else rate, np.float64)
+    if rows is None and horizon_s is not None:
+        rows = default_rows(r, horizon_s)
+    return batch.generate_arrivals(r[lo:hi] if r.ndim else float(r), horizon_s=horizon_s, rows=rows, seed=seed, epoch=epoch, env_offset=lo,
+                                   min_gap=min_gap, covered=covered)
+
+
 def metrics_vector(metrics, device, extra=()):
     return torch.tensor([metrics[k] for k in _capi.METRIC_NAMES] + [float(x) for x in extra], dtype=torch.float64,
                         device=device)
