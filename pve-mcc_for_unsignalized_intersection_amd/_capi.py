@@ -89,6 +89,12 @@ class PveArrivalGen(C.Structure):
                 ("mean_env", C.c_void_p), ("min_gap_s", C.c_double), ("block_threads", C.c_int32)]
 
 
+class PveStats(C.Structure):
+    _fields_ = [("n_ticks", C.c_int32), ("n_groups", C.c_int32), ("block_threads", C.c_int32), ("reserved", C.c_int32),
+                ("group", C.c_void_p), ("flags", C.c_void_p), ("reward", C.c_void_p), ("obs_pre", C.c_void_p), ("env_out", C.c_void_p),
+                ("series", C.c_void_p), ("totals", C.c_void_p), ("scratch", C.c_void_p)]
+
+
 class PveLearner(C.Structure):
     _fields_ = [("params", C.c_void_p), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
                 ("beta2", C.c_float), ("epsilon", C.c_float), ("tau", C.c_float), ("flags", C.c_int32), ("block_threads", C.c_int32)]
@@ -120,6 +126,9 @@ EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_works
            "pve_learner_step_wide", "pve_prio_scratch_bytes", "pve_prio_reset", "pve_prio_rank", "pve_prio_sample", "pve_prio_update")
 # entry points declared in extension headers (include/pve_env_arrivals.h), added within ABI 9 behind include/pve_env.h's 44
 EXPORTS_EXT = ("pve_generate_arrivals",)
+# ... and in include/pve_env_stats.h: roll-out and evaluation statistics by group (csrc/pve_stats.h)
+EXPORTS_STATS = ("pve_stats_scratch_bytes", "pve_rollout_stats", "pve_metrics_groups")
+PVE_STAT_N, PVE_STAT_MAX_GROUPS = 14, 1024
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -172,8 +181,12 @@ def _declare(L):
     L.pve_generate_arrivals.argtypes = [vp, C.POINTER(PveArrivalGen), vp, vp, vp]
     L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
     L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
-    for name in EXPORTS + EXPORTS_EXT:
-        if name not in ("pve_last_error", "pve_workspace_bytes", "pve_default_config", "pve_prio_scratch_bytes"):
+    L.pve_stats_scratch_bytes.restype = C.c_size_t
+    L.pve_stats_scratch_bytes.argtypes = [C.c_int, C.c_int]
+    L.pve_rollout_stats.argtypes = [vp, C.POINTER(PveStats)]
+    L.pve_metrics_groups.argtypes = [vp, vp, C.c_int, vp]
+    for name in EXPORTS + EXPORTS_EXT + EXPORTS_STATS:
+        if name not in ("pve_last_error", "pve_workspace_bytes", "pve_default_config", "pve_prio_scratch_bytes", "pve_stats_scratch_bytes"):
             getattr(L, name).restype = C.c_int
     L.pve_default_config.restype = None
     return L
@@ -192,7 +205,7 @@ def load_library(path=None):
         raise PveError("%s not found: build the HIP library first (python -c 'import __graft_entry__ as g; "
                        "g.build()' or make -C %s/csrc). There is no CPU fallback." % (p, _HERE))
     dll = C.CDLL(p)
-    missing = [n for n in EXPORTS + EXPORTS_EXT if not hasattr(dll, n)]
+    missing = [n for n in EXPORTS + EXPORTS_EXT + EXPORTS_STATS if not hasattr(dll, n)]
     if missing:       # (the target-network entry points were added within ABI 9: an older build lacks the symbols)
         raise PveError("%s is an older build: it lacks %s (rebuild it)" % (p, ", ".join(missing)))
     L = _declare(dll)

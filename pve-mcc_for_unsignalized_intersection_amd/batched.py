@@ -765,6 +765,98 @@ class BatchedIntersections:
         check(self.lib, self.lib.pve_get_metrics(self._h, out), "pve_get_metrics")
         return dict(zip(_capi.METRIC_NAMES, [float(x) for x in out]))
 
+    # ------------------------------------------------------------------ statistics by group (pve_rollout_stats / pve_metrics_groups)
+    def _groups_arg(self, groups, n_groups, what):
+        """(int32 device tensor [n_envs] or None, G).  The map's maximum is read only from a host array: a device tensor needs
+        n_groups (reading it would wait for the device)."""
+        if groups is None:
+            if n_groups not in (None, 1):
+                raise PveError("%s: n_groups must be 1 without a group map" % what)
+            return None, 1
+        if n_groups is None:
+            if torch.is_tensor(groups) and groups.device.type == "cuda":
+                raise PveError("%s: pass n_groups with a group map on the device" % what)
+            n_groups = int(np.max(groups.numpy() if torch.is_tensor(groups) else np.asarray(groups))) + 1
+        g = (groups if torch.is_tensor(groups) else torch.as_tensor(np.asarray(groups))).to(device=self.device, dtype=torch.int32).contiguous()
+        if tuple(g.shape) != (self.n_envs,):
+            raise PveError("%s: groups must be [n_envs]" % what)
+        return g, int(n_groups)
+
+    def _f64_arg(self, x, shape, what):
+        if x is None:
+            return torch.empty(shape, dtype=torch.float64, device=self.device)
+        if not torch.is_tensor(x) or x.dtype != torch.float64 or not x.is_contiguous() or tuple(x.shape) != tuple(shape) or \
+                x.device.type != self.device.type:
+            raise PveError("%s must be a contiguous float64 device tensor of shape %s" % (what, tuple(shape)))
+        return x
+
+    def rollout_stats(self, traj=None, groups=None, n_groups=None, out=None, totals=None, block_threads=0):
+        """The roll-out's statistics by tick and by group of environments (pve_rollout_stats; what main.py:286-304 writes per
+        tick and main.py:315-328 / :413-415 / :576-581 derive): the float64 device tensor series [T, G, 14], columns
+        stats.STAT_NAMES, bit-equal to stats.rollout_stats (csrc/pve_stats.h states the order of every sum).
+        traj: a dict of retained blocks (what step_many(trajectory=...) returned; [n_envs, ...] blocks count as T = 1) holding
+        flags, reward and env_out, and obs_pre when sum_v / sum_a are wanted (they are 0 without).  None: the blocks of the
+        last step_many(trajectory=...) when there was one, else the single-tick views.  groups: int [n_envs] with values in
+        [0, n_groups) (an environment outside the range is counted in no group), None = one group.  totals: a float64
+        device tensor [G, 14] to which series[t], t ascending, is added on the device: an epoch's totals across calls.
+        Runs on the batch's stream and reads nothing back; stats.summaries() turns series or totals into the reference's
+        quantities.  (The kernels' scratch, the per-(tick, env) rows [T, n_envs, 14], is kept in the batch and reused by the
+        next call of the same shape.)"""
+        with self._own_stream():
+            if traj is None:
+                last = getattr(self, "_last_traj", None)
+                traj = last[1] if last is not None and last[0] == self.ticks else self.out
+            for k in ("flags", "reward", "env_out"):
+                if k not in traj:
+                    raise PveError("rollout_stats: the blocks lack the %s output (create the batch with flags, reward, env_out)" % k)
+            E, K = self.n_envs, self.capacity
+            flags = traj["flags"]
+            T = 1 if flags.dim() == 2 else int(flags.shape[0])
+            want = dict(flags=((T, E, K), torch.int32), reward=((T, E, K), torch.float64), env_out=((T, E, 8), torch.int32),
+                        obs_pre=((T, E, K, 28), self.obs_dtype))
+            keep = {}
+            for k, (shp, dt) in want.items():
+                tns = traj.get(k)
+                if tns is None:
+                    continue
+                if not torch.is_tensor(tns) or tns.dtype != dt or tns.device.type != self.device.type or \
+                        tuple(tns.shape) not in (shp, shp[1:] if T == 1 else shp) or T < 1:
+                    raise PveError("rollout_stats: %s must be a %s device tensor of shape %s" % (k, dt, shp))
+                keep[k] = tns.contiguous()
+            g, G = self._groups_arg(groups, n_groups, "rollout_stats")
+            series = self._f64_arg(out, (T, G, _capi.PVE_STAT_N), "out")
+            if totals is not None:
+                totals = self._f64_arg(totals, (G, _capi.PVE_STAT_N), "totals")
+            rows = self.__dict__.get("_stats_rows")
+            if rows is None or tuple(rows.shape) != (T, E, _capi.PVE_STAT_N):
+                rows = torch.empty(T, E, _capi.PVE_STAT_N, dtype=torch.float64, device=self.device)
+            st = _capi.PveStats(n_ticks=T, n_groups=G, block_threads=int(block_threads), reserved=0,
+                                group=g.data_ptr() if g is not None else None, flags=keep["flags"].data_ptr(),
+                                reward=keep["reward"].data_ptr(), obs_pre=keep["obs_pre"].data_ptr() if "obs_pre" in keep else None,
+                                env_out=keep["env_out"].data_ptr(), series=series.data_ptr(),
+                                totals=totals.data_ptr() if totals is not None else None, scratch=rows.data_ptr())
+            self._bind_stream()
+            check(self.lib, self.lib.pve_rollout_stats(self._h, C.byref(st)), "pve_rollout_stats")
+            if self._stream_obj is not None and self.device.type == "cuda":
+                for tns in list(keep.values()) + ([g] if g is not None else []):
+                    tns.record_stream(self._stream_obj)
+            self._stats_rows = rows
+        return series
+
+    def metrics_by_group(self, groups=None, n_groups=None, out=None):
+        """The twelve sums of metrics() per group of environments, read from the per-environment headers on the device
+        (pve_metrics_groups): the float64 device tensor [G, 12] in the order of _capi.METRIC_NAMES, on the batch's stream, with
+        no host copy and no wait.  With one group it equals metrics() bit for bit.  groups / n_groups as rollout_stats."""
+        with self._own_stream():
+            g, G = self._groups_arg(groups, n_groups, "metrics_by_group")
+            res = self._f64_arg(out, (G, _capi.PVE_N_METRICS), "out")
+            self._bind_stream()
+            check(self.lib, self.lib.pve_metrics_groups(self._h, C.c_void_p(g.data_ptr()) if g is not None else None, G,
+                                                        C.c_void_p(res.data_ptr())), "pve_metrics_groups")
+            if g is not None and self._stream_obj is not None and self.device.type == "cuda":
+                g.record_stream(self._stream_obj)
+        return res
+
 
 
 class PipelinedIntersections:
@@ -964,6 +1056,73 @@ class PipelinedIntersections:
             m = sub.metrics()
             tot = m if tot is None else {k: tot[k] + m[k] for k in m}
         return tot
+
+    def _sum_of_subs(self, parts):
+        """parts[0] + parts[1] + ... in ascending sub-batch order on torch's current stream, which waits for every
+        sub-batch's stream first (event waits, no host synchronisation)."""
+        cur = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
+        res = None
+        for k, p in enumerate(parts):
+            if cur is not None and self.streams[k] is not None:
+                cur.wait_stream(self.streams[k])
+                p.record_stream(cur)
+            res = p.clone() if res is None else res + p
+        return res
+
+    def _groups_of_subs(self, groups, n_groups, what):
+        """(per-sub-batch maps, G).  A map on the device was produced on torch's current stream: every sub-batch's stream
+        waits for that stream (an event wait) before its kernels read their slice."""
+        if groups is None:
+            return [None] * self.n_sub, n_groups
+        on_device = torch.is_tensor(groups) and groups.device.type == "cuda"
+        if n_groups is None:
+            if on_device:
+                raise PveError("%s: pass n_groups with a group map on the device" % what)
+            n_groups = int(np.max(groups.numpy() if torch.is_tensor(groups) else np.asarray(groups))) + 1
+        if not torch.is_tensor(groups):
+            groups = np.asarray(groups)
+        if on_device:
+            self.wait_stream()
+            for s in self.streams:
+                groups.record_stream(s)
+        return self._parts(groups), n_groups
+
+    def _out_of_subs(self, out, parts):
+        res = self._sum_of_subs(parts)
+        if out is None:
+            return res
+        if not torch.is_tensor(out) or out.dtype != torch.float64 or tuple(out.shape) != tuple(res.shape) or out.device != res.device:
+            raise PveError("out must be a float64 device tensor of shape %s" % (tuple(res.shape),))
+        return out.copy_(res)
+
+    def rollout_stats(self, traj=None, groups=None, n_groups=None, out=None, totals=None, block_threads=0):
+        """BatchedIntersections.rollout_stats of every sub-batch on its own stream (traj: None, or the list step_many
+        returned; groups: [n_envs], cut at `bounds`; a map on the device is taken as produced on torch's current stream, which
+        the sub-batches' streams then wait for), the per-sub-batch series added in ascending sub-batch order:
+        series = (s_0 + s_1) + s_2 ... on torch's current stream, which waits for the sub-batches' streams.  The integer
+        columns are those of one batch of n_envs environments; the four float columns are another fixed order than that
+        batch's (one addition per sub-batch instead of one chain over all chunks), fixed by (n_envs, n_sub, the group map).
+        totals [G, 14]: series[t] is added to it for t ascending, on the same stream (one small addition per tick: the order
+        is the documented one, which a library reduction over t would not promise).  Returns the device tensor [T, G, 14]
+        (`out` when given)."""
+        gs, n_groups = self._groups_of_subs(groups, n_groups, "rollout_stats")
+        tr = traj if isinstance(traj, (list, tuple)) else [traj] * self.n_sub
+        parts = [sub.rollout_stats(tr[k], groups=gk, n_groups=n_groups, block_threads=block_threads)
+                 for k, (sub, gk) in enumerate(zip(self.subs, gs))]
+        series = self._out_of_subs(out, parts)
+        if totals is not None:
+            if totals.dtype != torch.float64 or tuple(totals.shape) != tuple(series.shape[1:]):
+                raise PveError("rollout_stats: totals must be a float64 device tensor [n_groups, 14]")
+            for t in range(series.shape[0]):
+                totals.add_(series[t])
+        return series
+
+    def metrics_by_group(self, groups=None, n_groups=None, out=None):
+        """BatchedIntersections.metrics_by_group of every sub-batch on its own stream, added in ascending sub-batch order on
+        torch's current stream (the counters exact; sum_reward / sum_jerk one addition per sub-batch).  groups as
+        rollout_stats.  Device tensor [G, 12] (`out` when given)."""
+        gs, n_groups = self._groups_of_subs(groups, n_groups, "metrics_by_group")
+        return self._out_of_subs(out, [sub.metrics_by_group(gk, n_groups) for sub, gk in zip(self.subs, gs)])
 
     def sub_of(self, env):
         """(sub-batch index, local env index) of a global env index."""

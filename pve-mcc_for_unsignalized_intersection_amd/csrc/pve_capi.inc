@@ -58,6 +58,10 @@
 //                                                // optional, all four or none: pve_prio_reset / _rank / _sample / _update (csrc/pve_prio.h)
 //     static int   launch_generate_arrivals(const pve::ArrivalArgs &, int block_threads, void *stream, std::string &err);
 //                                                // optional: pve_generate_arrivals (csrc/pve_arrivals.h)
+//     static int   launch_rollout_stats(const pve::StatsArgs &, int block_threads, void *stream, std::string &err);
+//     static int   launch_metrics_groups(const pve::EnvHeader *, int n_envs, int cap, const int32_t *group, int n_groups, double *out,
+//                                        void *stream, std::string &err);
+//                                                // optional, both or none: pve_rollout_stats / pve_metrics_groups (csrc/pve_stats.h)
 //     static int   launch_learner_init(float *params, const float *actor, const float *critic, const float *target_actor,
 //                                      const float *target_critic, float beta1, float beta2, void *stream, std::string &err);
 //     static int   launch_learner_step(const pve::LearnCtx &, int block_threads, void *stream, std::string &err);
@@ -303,6 +307,20 @@ template <class B, class = void> struct backend_arrivals {
 template <class B> struct backend_arrivals<B, decltype((void)&B::launch_generate_arrivals)> {
     static constexpr bool value = true;
     static int generate(const ArrivalArgs &A, int block, void *stream, std::string &err) { return B::launch_generate_arrivals(A, block, stream, err); }
+};
+// The statistics (pve_rollout_stats / pve_metrics_groups) need the kernels of pve_stats.h: Backend::launch_rollout_stats and
+// launch_metrics_groups (detected by the first).  A backend without them exports the entry points all the same; they validate
+// their arguments and then refuse with PVE_ERR_INVALID.
+template <class B, class = void> struct backend_stats {
+    static constexpr bool value = false;
+    static int rollout(const StatsArgs &, int, void *, std::string &) { return -1; }
+    static int metrics(const EnvHeader *, int, int, const int32_t *, int, double *, void *, std::string &) { return -1; }
+};
+template <class B> struct backend_stats<B, decltype((void)&B::launch_rollout_stats)> {
+    static constexpr bool value = true;
+    static int rollout(const StatsArgs &A, int block, void *stream, std::string &err) { return B::launch_rollout_stats(A, block, stream, err); }
+    static int metrics(const EnvHeader *hd, int n_envs, int cap, const int32_t *group, int n_groups, double *out, void *stream,
+                       std::string &err) { return B::launch_metrics_groups(hd, n_envs, cap, group, n_groups, out, stream, err); }
 };
 // The learner step (pve_learner_init / pve_learner_step) needs the kernels behind Backend::launch_learner_init /
 // launch_learner_step (detected by the second).  A backend without them exports the entry points all the same; they validate
@@ -990,6 +1008,63 @@ int pve_generate_arrivals(pve_handle h, const pve_arrival_gen *g, double *arriva
     std::string err;
     if (backend_arrivals<Backend>::generate(A, g->block_threads, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_generate_arrivals: " + err);
+    return PVE_OK;
+}
+
+// Roll-out and evaluation statistics (include/pve_env_stats.h; the definition is csrc/pve_stats.h).  `struct pve_stats` is the
+// public descriptor; this file reads it through its restatement StatsDesc (a translation unit that includes the public header
+// asserts that the two agree).
+struct pve_stats;
+
+size_t pve_stats_scratch_bytes(int n_envs, int n_ticks)
+{
+    if (n_envs < 1 || n_ticks < 1) return 0;
+    return stats_scratch_bytes(n_envs, n_ticks);
+}
+
+int pve_rollout_stats(pve_handle h, const struct pve_stats *st)
+{
+    const StatsDesc *d = (const StatsDesc *)st;
+    if (!h || !d) return fail(PVE_ERR_INVALID, "pve_rollout_stats: null handle or descriptor");
+    if (!d->flags || !d->reward || !d->env_out || !d->series || !d->scratch)
+        return fail(PVE_ERR_INVALID, "pve_rollout_stats: null flags, reward, env_out, series or scratch");
+    if (d->n_ticks < 1) return fail(PVE_ERR_INVALID, "pve_rollout_stats: n_ticks must be >= 1");
+    if (d->n_groups < 1 || d->n_groups > STAT_MAX_GROUPS || (!d->group && d->n_groups != 1))
+        return fail(PVE_ERR_INVALID, "pve_rollout_stats: n_groups must be 1 .. 1024, and 1 without a group map");
+    if (d->block_threads < 0 || d->block_threads > 1024 || d->block_threads % 64)
+        return fail(PVE_ERR_INVALID, "pve_rollout_stats: block_threads must be 0 or a multiple of 64 up to 1024");
+    if (d->reserved != 0) return fail(PVE_ERR_INVALID, "pve_rollout_stats: reserved must be 0");
+    const uintptr_t obs_mask = (h->cfg.flags & PVE_CFG_OBS_F32) ? 3 : 7;
+    if (((uintptr_t)d->group & 3) || ((uintptr_t)d->flags & 3) || ((uintptr_t)d->env_out & 3) || ((uintptr_t)d->reward & 7) ||
+        ((uintptr_t)d->obs_pre & obs_mask) || ((uintptr_t)d->series & 7) || ((uintptr_t)d->totals & 7) || ((uintptr_t)d->scratch & 7))
+        return fail(PVE_ERR_INVALID, "pve_rollout_stats: every block must be aligned to its element type");
+    if (h->cap % STAT_LANES) return fail(PVE_ERR_INVALID, "pve_rollout_stats: the capacity must be a multiple of 64");
+    if (!backend_stats<Backend>::value) return fail(PVE_ERR_INVALID, "pve_rollout_stats: this backend has no statistics kernels");
+    StatsArgs A;
+    A.n_envs = h->n_envs; A.cap = h->cap; A.n_ticks = d->n_ticks; A.n_groups = d->n_groups;
+    A.obs_f32 = (h->cfg.flags & PVE_CFG_OBS_F32) ? 1 : 0;
+    A.group = d->group; A.flags = d->flags; A.reward = d->reward; A.obs_pre = d->obs_pre; A.env_out = d->env_out;
+    A.series = d->series; A.totals = d->totals; A.scratch = (double *)d->scratch;
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_stats<Backend>::rollout(A, d->block_threads, h->stream, err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_rollout_stats: " + err);
+    return PVE_OK;
+}
+
+int pve_metrics_groups(pve_handle h, const int32_t *group, int n_groups, double *out)
+{
+    if (!h || !out) return fail(PVE_ERR_INVALID, "pve_metrics_groups: null handle or out");
+    if (n_groups < 1 || n_groups > STAT_MAX_GROUPS || (!group && n_groups != 1))
+        return fail(PVE_ERR_INVALID, "pve_metrics_groups: n_groups must be 1 .. 1024, and 1 without a group map");
+    if (((uintptr_t)group & 3) || ((uintptr_t)out & 7))
+        return fail(PVE_ERR_INVALID, "pve_metrics_groups: group must be 4-byte aligned, out 8-byte");
+    if (!backend_stats<Backend>::value) return fail(PVE_ERR_INVALID, "pve_metrics_groups: this backend has no statistics kernels");
+    DevScope dev_scope(h->device);
+    std::string err;
+    if (backend_stats<Backend>::metrics((const EnvHeader *)(h->ws + h->L.off_headers), h->n_envs, h->cap, group, n_groups, out, h->stream,
+                                        err) != 0)
+        return fail(PVE_ERR_NO_DEVICE, "pve_metrics_groups: " + err);
     return PVE_OK;
 }
 

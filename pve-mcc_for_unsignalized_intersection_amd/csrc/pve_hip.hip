@@ -16,6 +16,7 @@
 
 #include "pve_host.h"
 #include "../../include/pve_env_arrivals.h"      // (holds the definition in this translation unit to the public prototype)
+#include "../../include/pve_env_stats.h"         // (the same for pve_rollout_stats / pve_metrics_groups and their descriptor)
 #include "pve_tick_core.h"
 #include "pve_tick_geo.h"
 #include "pve_actor.h"
@@ -24,9 +25,31 @@
 #include "pve_replay.h"
 #include "pve_prio.h"
 #include "pve_arrivals.h"
+#include "pve_stats.h"
 #include "pve_learn.h"
 
 using namespace pve;
+
+// csrc/pve_stats.h restates the public descriptor and column numbers of include/pve_env_stats.h
+static_assert(sizeof(StatsDesc) == sizeof(pve_stats) && offsetof(StatsDesc, n_ticks) == offsetof(pve_stats, n_ticks) &&
+              offsetof(StatsDesc, n_groups) == offsetof(pve_stats, n_groups) && offsetof(StatsDesc, reserved) == offsetof(pve_stats, reserved) &&
+              offsetof(StatsDesc, group) == offsetof(pve_stats, group) &&
+              offsetof(StatsDesc, flags) == offsetof(pve_stats, flags) && offsetof(StatsDesc, reward) == offsetof(pve_stats, reward) &&
+              offsetof(StatsDesc, obs_pre) == offsetof(pve_stats, obs_pre) && offsetof(StatsDesc, env_out) == offsetof(pve_stats, env_out) &&
+              offsetof(StatsDesc, series) == offsetof(pve_stats, series) && offsetof(StatsDesc, totals) == offsetof(pve_stats, totals) &&
+              offsetof(StatsDesc, scratch) == offsetof(pve_stats, scratch) && offsetof(StatsDesc, block_threads) == offsetof(pve_stats, block_threads),
+              "pve_stats.h and pve_env_stats.h disagree on the descriptor");
+static_assert(STAT_N == PVE_STAT_N && STAT_MAX_GROUPS == PVE_STAT_MAX_GROUPS && STAT_N_METRICS == PVE_N_METRICS &&
+              (int)STAT_ENV_TICKS == PVE_STAT_ENV_TICKS && (int)STAT_ALIVE == PVE_STAT_ALIVE && (int)STAT_SPAWNED == PVE_STAT_SPAWNED &&
+              (int)STAT_FINISHED == PVE_STAT_FINISHED && (int)STAT_DELETED == PVE_STAT_DELETED && (int)STAT_COLLISIONS == PVE_STAT_COLLISIONS &&
+              (int)STAT_LOCK == PVE_STAT_LOCK && (int)STAT_CTL == PVE_STAT_CTL && (int)STAT_COLLIDED == PVE_STAT_COLLIDED &&
+              (int)STAT_DONE == PVE_STAT_DONE && (int)STAT_SUM_REWARD == PVE_STAT_SUM_REWARD &&
+              (int)STAT_SUM_REWARD_SQ == PVE_STAT_SUM_REWARD_SQ && (int)STAT_SUM_V == PVE_STAT_SUM_V && (int)STAT_SUM_A == PVE_STAT_SUM_A &&
+              STAT_F_CTL == PVE_F_CTL && STAT_F_DONE == PVE_F_DONE, "pve_stats.h and the public headers disagree on the columns");
+static_assert(((STAT_EO_OF_COLUMN >> 0) & 7) == PVE_EO_N_PRE && ((STAT_EO_OF_COLUMN >> 4) & 7) == PVE_EO_N_SPAWNED &&
+              ((STAT_EO_OF_COLUMN >> 8) & 7) == PVE_EO_N_FINISHED && ((STAT_EO_OF_COLUMN >> 12) & 7) == PVE_EO_N_DELETED &&
+              ((STAT_EO_OF_COLUMN >> 16) & 7) == PVE_EO_COLLISIONS && ((STAT_EO_OF_COLUMN >> 20) & 7) == PVE_EO_LOCK,
+              "pve_stats.h and pve_env.h disagree on env_out");
 
 // A/B knobs of the measurement tooling (tools/ab_launch_shapes.py, tools/gpu.sh): environment variables that switch launch
 // shapes.  Compiled in only with -DPVE_AB_KNOBS (`make knobs` -> build/libpveenv_knobs.so); the product library reads no
@@ -1664,6 +1687,26 @@ struct Backend {
             const long long items = (((long long)A.rows + ARR_INT_ROWS - 1) / ARR_INT_ROWS) * A.n_envs;
             hipLaunchKernelGGL(k_gen_intentions, dim3((unsigned)(items < (1 << 20) ? items : (1 << 20))), dim3(block), 0, s, A);
         }
+        return check_launch(err);
+    }
+    // pve_rollout_stats: the env rows (one wave per (tick, env)), the groups (one workgroup per (tick, group)), the totals
+    static int launch_rollout_stats(const StatsArgs &A, int block_threads, void *stream, std::string &err)
+    {
+        hipStream_t s = (hipStream_t)stream;
+        const int block = block_threads > 0 ? block_threads : 256;
+        const long long items = (long long)A.n_ticks * A.n_envs, per = block / 64, want = (items + per - 1) / per;
+        hipLaunchKernelGGL(k_stats_rows, dim3((unsigned)(want < (1 << 16) ? want : (1 << 16))), dim3(block), 0, s, A);
+        // (few workgroups, each walking every chunk of its tick: sixteen waves by default, so that a wave has few chunks in a row)
+        hipLaunchKernelGGL(k_stats_groups, dim3((unsigned)A.n_ticks, (unsigned)A.n_groups), dim3(block_threads > 0 ? block_threads : 1024), 0, s, A);
+        if (A.totals)
+            hipLaunchKernelGGL(k_stats_totals, dim3((unsigned)((A.n_groups * STAT_N + 255) / 256)), dim3(256), 0, s, A);
+        return check_launch(err);
+    }
+    // pve_metrics_groups: one workgroup per group
+    static int launch_metrics_groups(const EnvHeader *hd, int n_envs, int cap, const int32_t *group, int n_groups, double *out,
+                                     void *stream, std::string &err)
+    {
+        hipLaunchKernelGGL(k_stats_metrics, dim3((unsigned)n_groups), dim3(STAT_METRIC_THREADS), 0, (hipStream_t)stream, hd, n_envs, cap, group, n_groups, out);
         return check_launch(err);
     }
     static int launch_probe(const Params &P, int cap, int *sink, void *stream, std::string &err)

@@ -13,6 +13,7 @@
 #include "pve_replay.h"
 #include "pve_prio.h"
 #include "pve_arrivals.h"
+#include "pve_stats.h"
 #include "pve_learn.h"
 
 namespace pve {

@@ -7,13 +7,19 @@ the aggregate lines of main.py:523-526 / 576-581 are printed from the metrics ve
     vehicle number, collisions occurred number, collisions rate, pT-m (mean passing time), mean jerk, lock_num
 
 One arrival stream can be replicated over many environments (`--envs`, independent copies are identical) or a
-synthetic batch can be evaluated (`--synthetic RATE`)."""
+synthetic batch can be evaluated (`--synthetic RATE`).
+
+`--rates 1200,1000,900,800,600,400,200` is batch_test()'s sweep over densities (main.py:543-583) as ONE batch: every density
+gets `--envs` environments whose arrival streams are generated on the device at its rate, the environments are grouped by
+density, and one line per density is printed in batch_test()'s wording from the grouped metrics and roll-out statistics
+(metrics_by_group / rollout_stats), read back once at the end."""
 import argparse
 import json
 
 import numpy as np
 
 from .arrivals import load_arrival_mat, pad_stream, synthetic_arrivals, synthetic_intentions
+from ._capi import METRIC_NAMES as _METRIC_NAMES
 from .batched import BatchedIntersections
 
 
@@ -38,6 +44,55 @@ def evaluate(arrivals, weights, ticks=1000, n_envs=1, capacity=128, device="cuda
     }
 
 
+def evaluate_rates(rates, weights, ticks=1000, envs_per_rate=1, capacity=128, device="cuda", seed=20250213, epoch=0, chunk=50,
+                   **config):
+    """batch_test() (main.py:543-583) over several densities in one batch: len(rates) x envs_per_rate environments, the
+    arrival stream of each generated on the device at its rate (generate_arrivals), grouped by rate.  The closed loop runs
+    in calls of `chunk` ticks into one reused trajectory buffer; after every call rollout_stats adds the call's ticks to the
+    per-rate totals on the device; metrics_by_group reads the headers at the end.  One read-back, after the last tick.
+    -> list of one dict per rate (the order of `rates`) with the quantities of main.py:576-581 and the reward mean / standard
+    deviation over controlled vehicles (main.py:573-574 prints them for one tick; here they cover the run)."""
+    import torch
+    from . import stats
+    rates = [float(r) for r in rates]
+    R, n = len(rates), int(envs_per_rate)
+    env = BatchedIntersections(R * n, capacity, None, device=device, outputs=("obs_post", "obs_pre", "reward", "flags", "env_out"),
+                               **config)
+    dt = float(env.cfg.deltaT)
+    env.generate_arrivals(np.repeat(np.asarray(rates), n), horizon_s=ticks * dt + 30.0, seed=seed, epoch=epoch)
+    groups = torch.as_tensor(np.repeat(np.arange(R, dtype=np.int32), n)).to(env.device)
+    env.set_actor(weights)
+    env.reset()
+    ring = env.alloc_trajectory(min(chunk, ticks))
+    totals = torch.zeros(R, stats.STAT_N, dtype=torch.float64, device=env.device)
+    done = 0
+    while done < ticks:
+        k = min(chunk, ticks - done)
+        env.step_many(k, source="actor", trajectory=ring)
+        env.rollout_stats(groups=groups, n_groups=R, totals=totals)
+        done += k
+    m = env.metrics_by_group(groups, R).cpu().numpy()                       # the one read-back (waits for the stream)
+    s = stats.summaries(totals)
+    col = {name: k for k, name in enumerate(_METRIC_NAMES)}
+    out = []
+    for g, rate in enumerate(rates):
+        spawned, passed, collided = m[g, col["spawned"]], m[g, col["passed"]], m[g, col["collided"]]
+        out.append({"rate": rate, "vehicles": spawned, "passed": passed, "collisions": collided,
+                    "collisions_rate": collided / max(spawned, 1.0),
+                    "pT_m": m[g, col["passed_steps"]] / (passed + 1e-4) * dt,            # main.py:579
+                    "jerk_mean": m[g, col["sum_jerk"]] / max(passed, 1.0),                # main.py:580
+                    "lock_num": m[g, col["locks"]], "reward_mean": float(s["reward_mean"][g]), "reward_std": float(s["reward_std"][g]),
+                    "v_mean": float(s["v_mean"][g]),
+                    "ticks": ticks, "n_envs": n, "overflow": m[g, col["overflow"]]})
+    return out
+
+
+def rate_line(res):
+    """One density's result in the wording of batch_test() (main.py:576-581)"""
+    return "vehicle number %d  collisions occurred number %d collisions rate %s pT-m %0.4f s jerks %s lock_num %d" % (
+        res["vehicles"], res["collisions"], res["collisions_rate"], res["pT_m"], res["jerk_mean"], res["lock_num"])
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--mat", help="MATLAB v5 arrival stream (variable arvTimeNewVeh)")
@@ -49,9 +104,20 @@ def main():
     ap.add_argument("--vm", type=float, default=5.0)
     ap.add_argument("--lane-num", type=int, default=12, choices=(12, 8, 4), help="main.py --lane_num (:101)")
     ap.add_argument("--seed", type=int, default=20250213, help="synthetic streams / 8-lane intention draws")
+    ap.add_argument("--rates", help="comma-separated veh/h/lane, e.g. 1200,1000,900,800,600,400,200: batch_test()'s densities in "
+                                    "one batch of --envs environments each, streams generated on the device; one line per density")
     a = ap.parse_args()
     z = np.load(a.weights)
     weights = {k: z[k] for k in z.files}
+    if a.rates:
+        rates = [float(x) for x in a.rates.split(",") if x.strip()]
+        results = evaluate_rates(rates, weights, ticks=a.ticks, envs_per_rate=a.envs, capacity=a.capacity, seed=a.seed, vm=a.vm,
+                                 lane_num=a.lane_num)
+        for res in results:
+            print("rate %g veh/h/lane x %d envs" % (res["rate"], res["n_envs"]))
+            print(rate_line(res))
+        print(json.dumps(results))
+        return
     if a.mat:
         arr = pad_stream(load_arrival_mat(a.mat))
     else:

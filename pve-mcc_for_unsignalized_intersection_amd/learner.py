@@ -14,7 +14,9 @@ Per step, in the reference's order:
   3. target = c1 * online + c2 * target for both networks, c1 = float32(1 - tau), c2 = float32(tau) (main.py:30).
 Adam is tf.train.AdamOptimizer's update (TF 1.x ApplyAdam) as the header writes it down; it is this library's definition.
 Not part of the step: td_error / update_priority (main.py:76-79, dead with rand_s=True) are critic_q() on the sampled rows and
-PrioritizedReplayMemory.update_priority (replay.py).  Not reproduced: the summaries."""
+PrioritizedReplayMemory.update_priority (replay.py).  The summaries main.py:286-304 writes per tick, and the collision rate that
+keeps best.cptk (main.py:315-328), come from the roll-out's own outputs: BatchedIntersections.rollout_stats and stats.summaries
+(stats.py)."""
 import ctypes as C
 
 import numpy as np
