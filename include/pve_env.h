@@ -659,7 +659,13 @@ int pve_get_metrics(pve_handle h, double out[PVE_N_METRICS]);
 
 /* Device views of the persistent per-slot state for zero-copy consumers (actor input masks):
  * field = "p","v","a","jerk","jerk_sum","vir_dis","closer_p" (float64 [n_envs][cap]) or
- * "id","seq","vnum","step","count","meta","hdr" (int32 [n_envs][cap]); meta bit0 = control. */
+ * "id","seq","vnum","step","count","meta","hdr" (int32 [n_envs][cap]); meta bit0 = control.
+ * Value range of a caller's writes: "seq" (seq_in_lane: the row of the arrival stream the vehicle came from) and "vnum"
+ * (id_info[1]) are carried by the 128-slot queue form of pve_step_many in ONE packed word, seq << 8 | vnum, so there
+ *   0 <= seq < 2^23   and   0 <= vnum < 256
+ * must hold.  The library's own values keep to it: vnum is a lane's vehicle count (at most the capacity), and a stream of
+ * rows >= 2^23, whose cursors could pass the range, takes the kernel build that carries the two fields in registers
+ * (pve_debug_last_variant: waves_per_simd 4 instead of 5).  Tested at the top of the range, seq = 2^23 - 2 .. 2^23 - 129. */
 int pve_state_field(pve_handle h, const char *field, void **dev_ptr, int *elem_bytes);
 #define PVE_META_CONTROL 0x1
 #define PVE_META_FINISH  0x2
@@ -668,12 +674,24 @@ int pve_state_field(pve_handle h, const char *field, void **dev_ptr, int *elem_b
 
 int pve_synchronize(pve_handle h);
 
-/* Diagnostics: accumulate per-phase clock ticks of every wave of the tick kernel into a zeroed DEVICE
- * buffer of uint64 [n_envs * capacity/64][16] (column = phase: load, step1, step2, step3, build, rank,
- * walk, effects, lock, final, state); NULL disables. Used by tools/phase_profile.py; no effect on results. */
+/* Diagnostics: accumulate per-phase clock ticks (wall_clock64: the 100 MHz constant clock) of every wave of the tick kernel into a
+ * zeroed DEVICE buffer of uint64 [n_envs * capacity/64][16], one row per wave, added to by every armed launch; NULL disables.
+ * The kernels write twelve columns (tools/phase_profile.py: PHASES):
+ *   0 load, 1 step1, 2 step2+listsA, 3 step3+listsB, 4 build, 5 rank, 6 reward+xy (behind the walk, with the closing barrier),
+ *   7 effects, 8 lock, 9 final, 10 state (the state_pre pass: 0 when it is not requested; 12 lanes), 11 walk(merge)
+ * and the diagnostics build of the resident roll-out kernel (PHASES_MANY: 0 = the reload barrier, 10 = stage+reload) two more:
+ *   12 shader-clock cycles of the launch (clock64), 13 its wall_clock64 ticks (12 / 13 = shader clock in units of 100 MHz);
+ * columns 14 and 15 are never written.  Used by tools/phase_profile.py; no effect on results (tested: state, outputs and metrics
+ * of an armed batch equal its twin's bit for bit).
+ * While armed, the stepping calls launch the diagnostics builds (pve_debug_last_variant: prof = 1): pve_step_all and the 4- / 8-lane
+ * ticks as usual; pve_step_many with PVE_SRC_ZERO / PVE_SRC_POOL, 64 or 128 slots, 12 lanes and no training outputs in the resident
+ * kernel (persistent = 1: as chunked launches); every other configuration as one launch per tick -- except PVE_SRC_TABLE, which has
+ * no per-tick form and is REFUSED with PVE_ERR_STATE while armed (lane_num 12, 4 and 8; nothing is launched, state and tick count
+ * stay as they were; the same call succeeds after pve_debug_phase_cycles(h, NULL)). */
 int pve_debug_phase_cycles(pve_handle h, uint64_t *dev_counters16);
 
-/* Diagnostics: what the last stepping call on this handle launched. */
+/* Diagnostics: what the last stepping call on this handle launched.  (Which kernel variant behind the form: the extension header
+ * include/pve_env_debug.h.) */
 enum { PVE_LAUNCH_NONE = 0, PVE_LAUNCH_TICK = 1 /* one launch per tick */, PVE_LAUNCH_RESIDENT = 2 /* one k_rollout launch per chunk */,
        PVE_LAUNCH_PERSISTENT = 3 /* ONE launch for the call, items pulled from the work queue */ };
 int pve_debug_last_launch(pve_handle h);
@@ -684,8 +702,8 @@ int pve_debug_last_launch(pve_handle h);
 int pve_debug_item_schedule(int n_ticks, int chunk_ticks, int32_t out[12]);
 
 /* Diagnostics: every later pve_step_all / pve_scene_update launch of the 12-lane kernel (k_tick) RETURNS behind phase n
- * (0 load, 1 step1, 2 step2, 3 step3, 4 build, 5 rank, 6 walk + reward, 7 effects, 8 lock) without writing any state, so
- * that hardware counters of truncated launches on one frozen state attribute instructions and LDS conflicts to phases
+ * (0 load, 1 step1, 2 step2, 3 step3, 4 build, 5 rank, 6 walk + reward, 7 effects, 8 lock) without writing any state (tested: the fourteen state
+ * fields, the headers and the metrics are bit-identical behind a truncated launch, for every n and capacity), so that hardware counters of truncated launches on one frozen state attribute instructions and LDS conflicts to phases
  * (tools/phase_counters.sh); n < 0 restores the full tick.  The results of truncated launches are meaningless. */
 int pve_debug_stop_phase(pve_handle h, int n);
 

@@ -95,6 +95,11 @@ class PveStats(C.Structure):
                 ("series", C.c_void_p), ("totals", C.c_void_p), ("scratch", C.c_void_p)]
 
 
+class PveLaunchVariant(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kind", "family", "capacity", "waves_per_simd", "prof", "actor", "train", "table",
+                                         "persistent", "geo", "grid", "launches")] + [("reserved", C.c_int32 * 4)]
+
+
 class PveLearner(C.Structure):
     _fields_ = [("params", C.c_void_p), ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("beta1", C.c_float),
                 ("beta2", C.c_float), ("epsilon", C.c_float), ("tau", C.c_float), ("flags", C.c_int32), ("block_threads", C.c_int32)]
@@ -129,6 +134,8 @@ EXPORTS_EXT = ("pve_generate_arrivals",)
 # ... and in include/pve_env_stats.h: roll-out and evaluation statistics by group (csrc/pve_stats.h)
 EXPORTS_STATS = ("pve_stats_scratch_bytes", "pve_rollout_stats", "pve_metrics_groups")
 PVE_STAT_N, PVE_STAT_MAX_GROUPS = 14, 1024
+# ... and in include/pve_env_debug.h: which kernel variant the last stepping call launched
+EXPORTS_DEBUG = ("pve_debug_last_variant",)
 LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
 
 
@@ -185,7 +192,12 @@ def _declare(L):
     L.pve_stats_scratch_bytes.argtypes = [C.c_int, C.c_int]
     L.pve_rollout_stats.argtypes = [vp, C.POINTER(PveStats)]
     L.pve_metrics_groups.argtypes = [vp, vp, C.c_int, vp]
-    for name in EXPORTS + EXPORTS_EXT + EXPORTS_STATS:
+    # (_declare also dresses libraries that load_library has not vetted -- the tests' emulators, which may be builds of sources
+    #  older than include/pve_env_debug.h: the diagnostics hook is declared where it exists, and last_variant() says so where not)
+    debug = tuple(n for n in EXPORTS_DEBUG if hasattr(L, n))
+    if debug:
+        L.pve_debug_last_variant.argtypes = [vp, C.POINTER(PveLaunchVariant)]
+    for name in EXPORTS + EXPORTS_EXT + EXPORTS_STATS + debug:
         if name not in ("pve_last_error", "pve_workspace_bytes", "pve_default_config", "pve_prio_scratch_bytes", "pve_stats_scratch_bytes"):
             getattr(L, name).restype = C.c_int
     L.pve_default_config.restype = None
@@ -205,7 +217,7 @@ def load_library(path=None):
         raise PveError("%s not found: build the HIP library first (python -c 'import __graft_entry__ as g; "
                        "g.build()' or make -C %s/csrc). There is no CPU fallback." % (p, _HERE))
     dll = C.CDLL(p)
-    missing = [n for n in EXPORTS + EXPORTS_EXT + EXPORTS_STATS if not hasattr(dll, n)]
+    missing = [n for n in EXPORTS + EXPORTS_EXT + EXPORTS_STATS + EXPORTS_DEBUG if not hasattr(dll, n)]
     if missing:       # (the target-network entry points were added within ABI 9: an older build lacks the symbols)
         raise PveError("%s is an older build: it lacks %s (rebuild it)" % (p, ", ".join(missing)))
     L = _declare(dll)

@@ -747,6 +747,20 @@ class BatchedIntersections:
             check(self.lib, k if k < 0 else -1, "pve_debug_last_launch")
         return ("none", "tick", "resident", "persistent")[k]
 
+    def last_variant(self):
+        """Which kernel variant the last stepping call launched, as a dict (pve_debug_last_variant, include/pve_env_debug.h):
+        kind (as last_launch()), family (12, or 4 / 8), capacity, waves_per_simd (4 = the register build, 5 = the HOME build
+        of the 128-slot queue kernel, 0 = per-tick launches), the flags prof / actor / train / table / persistent / geo of the
+        kernel that ran, grid (workgroups of the last launch) and launches (kernel launches the call enqueued).  Host only:
+        waits for nothing.  A call of zero ticks: kind "none" and zeros."""
+        v = _capi.PveLaunchVariant()
+        if not hasattr(self.lib, "pve_debug_last_variant"):
+            raise PveError("this library is an older build: it lacks pve_debug_last_variant (rebuild it)")
+        check(self.lib, self.lib.pve_debug_last_variant(self._h, C.byref(v)), "pve_debug_last_variant")
+        d = {n: int(getattr(v, n)) for n, _t in _capi.PveLaunchVariant._fields_ if n != "reserved"}
+        d["kind"] = ("none", "tick", "resident", "persistent")[d["kind"]]
+        return d
+
     # ------------------------------------------------------------------ host read-back
     def read_env(self, env=0):
         info = PveEnvInfo()
@@ -1049,6 +1063,14 @@ class PipelinedIntersections:
     def synchronize(self):
         for sub in self.subs:
             sub.synchronize()
+
+    def last_launch(self):
+        """last_launch() of every sub-batch, in order"""
+        return [sub.last_launch() for sub in self.subs]
+
+    def last_variant(self):
+        """last_variant() of every sub-batch, in order (each sub-batch is a handle of its own and launches for itself)"""
+        return [sub.last_variant() for sub in self.subs]
 
     def metrics(self):
         tot = None

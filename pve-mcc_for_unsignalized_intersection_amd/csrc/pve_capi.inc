@@ -420,6 +420,7 @@ int pve_create(const pve_config *cfg, int n_envs, int capacity, int device_id, v
     h->has_tactor = false; h->has_critic = false;
     h->q_done_base = 0;
     h->last_launch_kind = PVE_LAUNCH_NONE;
+    memset(&h->last_variant, 0, sizeof(h->last_variant));
     h->stop_phase = -1;
     memset(&h->noise, 0, sizeof(h->noise));
     *out = h;
@@ -506,6 +507,19 @@ static int tick_params(pve_handle h, const double *actions, const pve_outputs *o
     return PVE_OK;
 }
 
+// pve_debug_last_variant: a stepping call clears the thread's launch note and the handle's record in front of its launches and
+// copies the note -- what the backend wrote where it launched -- into the handle behind every launch that succeeded
+static void clear_variant(pve_handle h)
+{
+    memset(&launch_note(), 0, sizeof(LaunchVariant));
+    memset(&h->last_variant, 0, sizeof(h->last_variant));
+}
+static void commit_variant(pve_handle h)
+{
+    h->last_variant = launch_note();
+    h->last_variant.kind = h->last_launch_kind;
+}
+
 static int launch_one_tick(pve_handle h, const Params &P, const char *who)
 {
     DevScope dev_scope(h->device);
@@ -515,14 +529,18 @@ static int launch_one_tick(pve_handle h, const Params &P, const char *who)
     if (rc != 0) return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err);
     h->ticks_since_reset += 1;
     h->last_launch_kind = PVE_LAUNCH_TICK;
+    commit_variant(h);
     return PVE_OK;
 }
 
-static int run_tick(pve_handle h, const double *actions, const pve_outputs *out, int mode, const char *who)
+static int run_tick(pve_handle h, const double *actions, const pve_outputs *out, int mode, const char *who, int launches_before = 0)
 {
     Params P;
     const int rc = tick_params(h, actions, out, mode, who, P);
     if (rc != PVE_OK) return rc;
+    h->last_launch_kind = PVE_LAUNCH_NONE;
+    clear_variant(h);
+    launch_note().launches = launches_before;       // (pve_step_all_actor: the actor pass in front of the tick)
     return launch_one_tick(h, P, who);
 }
 
@@ -1086,7 +1104,7 @@ int pve_step_all_actor(pve_handle h, const float *weights, const void *obs_in, d
         return fail(PVE_ERR_INVALID, "pve_step_all_actor: with state_pre, out->obs_post must not alias obs_in (ping-pong them)");
     int rc = pve_actor_forward(h, weights, obs_in, actions);
     if (rc != PVE_OK) return rc;
-    return run_tick(h, actions, out, MODE_FUSED, "pve_step_all_actor");
+    return run_tick(h, actions, out, MODE_FUSED, "pve_step_all_actor", 1);
 }
 
 int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
@@ -1110,6 +1128,7 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
     int rc = tick_params(h, nullptr, out, MODE_FUSED, who, P);
     if (rc != PVE_OK) return rc;
     h->last_launch_kind = PVE_LAUNCH_NONE;          // (a call of zero ticks launches nothing)
+    clear_variant(h);
     if (ro->n_ticks == 0) return PVE_OK;
     if (ro->source == PVE_SRC_ACTOR) {
         rc = use_actor(h, ro->actor_weights, who);
@@ -1149,6 +1168,7 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
             h->q_done_base += (unsigned)(R.n_full + R.n_taper);
             h->ticks_since_reset += ro->n_ticks;
             h->last_launch_kind = PVE_LAUNCH_PERSISTENT;
+            commit_variant(h);
             return PVE_OK;
         }
         // (no persistent kernel for this configuration: chunked launches below)
@@ -1180,13 +1200,16 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
                                   : backend_noise<Backend>::launch_rollout(h->c, P, R, nz, h->cap, h->stream, err);
             if (rr < 0) return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err);
             if (rr > 0) {
-                if (ro->source == PVE_SRC_TABLE)
-                    return fail(PVE_ERR_STATE, std::string(who) + ": PVE_SRC_TABLE runs in the resident kernel only");
+                if (ro->source == PVE_SRC_TABLE)        // (nothing was launched: state and tick count are as before the call)
+                    return fail(PVE_ERR_STATE, std::string(who) + (h->phase_cycles
+                        ? ": PVE_SRC_TABLE runs in the resident kernel only, which has no phase-cycle build: disarm pve_debug_phase_cycles (NULL) first"
+                        : ": PVE_SRC_TABLE runs in the resident kernel only"));
                 if (k0 == 0) break;                 // no resident kernel for this configuration: per-tick launches below
                 return fail(PVE_ERR_STATE, std::string(who) + ": resident kernel refused a later chunk");
             }
             h->ticks_since_reset += R.n_ticks;
             h->last_launch_kind = PVE_LAUNCH_RESIDENT;
+            commit_variant(h);
             if (k0 + R.n_ticks >= ro->n_ticks) return PVE_OK;
         }
         P.out = o0;
@@ -1202,6 +1225,7 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
             P.actions = ro->pool + (size_t)(((long long)ro->pool_tick0 + k) % ro->n_pool) * (size_t)(E * cap);
         else if (ro->source == PVE_SRC_ACTOR) {
             if (run_actor(h, obs_in, ro->actor_actions, err) != 0) return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err);
+            launch_note().launches += 1;
             P.actions = ro->actor_actions;
             obs_in = P.out.obs_post;
         }
@@ -1364,6 +1388,16 @@ int pve_debug_last_launch(pve_handle h)
 {
     if (!h) return fail(PVE_ERR_INVALID, "pve_debug_last_launch: null handle");
     return h->last_launch_kind;
+}
+
+// `struct pve_launch_variant` (include/pve_env_debug.h) is read through its restatement LaunchVariant (pve_host.h), like pve_stats
+struct pve_launch_variant;
+
+int pve_debug_last_variant(pve_handle h, struct pve_launch_variant *out)
+{
+    if (!h || !out) return fail(PVE_ERR_INVALID, "pve_debug_last_variant: null handle or out");
+    *(LaunchVariant *)out = h->last_variant;
+    return PVE_OK;
 }
 
 int pve_debug_item_schedule(int n_ticks, int chunk_ticks, int32_t out[12])

@@ -17,6 +17,7 @@
 #include "pve_host.h"
 #include "../../include/pve_env_arrivals.h"      // (holds the definition in this translation unit to the public prototype)
 #include "../../include/pve_env_stats.h"         // (the same for pve_rollout_stats / pve_metrics_groups and their descriptor)
+#include "../../include/pve_env_debug.h"         // (the same for pve_debug_last_variant and its record)
 #include "pve_tick_core.h"
 #include "pve_tick_geo.h"
 #include "pve_actor.h"
@@ -50,6 +51,16 @@ static_assert(((STAT_EO_OF_COLUMN >> 0) & 7) == PVE_EO_N_PRE && ((STAT_EO_OF_COL
               ((STAT_EO_OF_COLUMN >> 8) & 7) == PVE_EO_N_FINISHED && ((STAT_EO_OF_COLUMN >> 12) & 7) == PVE_EO_N_DELETED &&
               ((STAT_EO_OF_COLUMN >> 16) & 7) == PVE_EO_COLLISIONS && ((STAT_EO_OF_COLUMN >> 20) & 7) == PVE_EO_LOCK,
               "pve_stats.h and pve_env.h disagree on env_out");
+
+// csrc/pve_host.h restates the record of include/pve_env_debug.h
+static_assert(sizeof(LaunchVariant) == sizeof(pve_launch_variant) && offsetof(LaunchVariant, kind) == offsetof(pve_launch_variant, kind) &&
+              offsetof(LaunchVariant, family) == offsetof(pve_launch_variant, family) && offsetof(LaunchVariant, capacity) == offsetof(pve_launch_variant, capacity) &&
+              offsetof(LaunchVariant, waves_per_simd) == offsetof(pve_launch_variant, waves_per_simd) && offsetof(LaunchVariant, prof) == offsetof(pve_launch_variant, prof) &&
+              offsetof(LaunchVariant, actor) == offsetof(pve_launch_variant, actor) && offsetof(LaunchVariant, train) == offsetof(pve_launch_variant, train) &&
+              offsetof(LaunchVariant, table) == offsetof(pve_launch_variant, table) && offsetof(LaunchVariant, persistent) == offsetof(pve_launch_variant, persistent) &&
+              offsetof(LaunchVariant, geo) == offsetof(pve_launch_variant, geo) && offsetof(LaunchVariant, grid) == offsetof(pve_launch_variant, grid) &&
+              offsetof(LaunchVariant, launches) == offsetof(pve_launch_variant, launches) && offsetof(LaunchVariant, reserved) == offsetof(pve_launch_variant, reserved),
+              "pve_host.h and pve_env_debug.h disagree on the launch record");
 
 // A/B knobs of the measurement tooling (tools/ab_launch_shapes.py, tools/gpu.sh): environment variables that switch launch
 // shapes.  Compiled in only with -DPVE_AB_KNOBS (`make knobs` -> build/libpveenv_knobs.so); the product library reads no
@@ -1154,7 +1165,8 @@ template <typename F, typename... Bs> static int with_flags(F f, bool b, Bs... r
 // whose occupancy sizes the persistent grid, and kernel() is the only place in the host code that writes k_rollout<..> with
 // arguments (tools/probe_kernel.sh's instantiation aside).
 template <int CAP_, int WPE_, bool PROF_, bool ACT_, bool TRAIN_, bool IDT_, bool PERS_> struct Rollout12 {
-    static constexpr int CAP = CAP_;
+    static constexpr int CAP = CAP_, WPE = WPE_;
+    static constexpr bool GEO = false, PROF = PROF_, ACT = ACT_, TRAIN = TRAIN_, IDT = IDT_;    // (what launch_variant notes)
     static constexpr bool PERS = PERS_, exists =
         !(PERS_ && PROF_) && !(ACT_ && IDT_) &&                                       // (the kernel's own static_asserts)
         (WPE_ == 4 ? !PROF_ || (CAP_ <= 128 && !ACT_ && !TRAIN_ && !IDT_)            // the phase-cycle diagnostics: the default kernel at 64 / 128 slots
@@ -1172,7 +1184,8 @@ template <int CAP_, int WPE_, bool PROF_, bool ACT_, bool TRAIN_, bool IDT_, boo
 // ... and of k_rollout_geo, which takes its arguments in another order: layout x capacity x {default, training outputs, id-indexed
 // table, actor, actor + training outputs} x launch form
 template <int CAP_, bool FIX4_, int WPE_, bool TRAIN_, bool IDT_, bool PERS_, bool ACT_> struct RolloutGeo {
-    static constexpr int CAP = CAP_;
+    static constexpr int CAP = CAP_, WPE = WPE_;
+    static constexpr bool GEO = true, PROF = false, ACT = ACT_, TRAIN = TRAIN_, IDT = IDT_;
     static constexpr bool PERS = PERS_, exists =
         !(TRAIN_ && IDT_) && !(ACT_ && IDT_) &&                                       // (the kernel's own static_asserts)
         CAP_ <= 128 && !(PERS_ && TRAIN_ && ACT_) &&                                  // (the 4- / 8-lane layouts: 64 or 128 slots)
@@ -1300,7 +1313,11 @@ struct Backend {
     }
     static int launch_tick(const Const &c, const Params &P, int cap, void *stream, std::string &err)
     {
-        return with_cap(cap, err, [&](auto CAP) { return launch(k_tick<CAP()>, P.n_envs, CAP(), stream, err, c, P); });
+        return with_cap(cap, err, [&](auto CAP) {
+            const int rc = launch(k_tick<CAP()>, P.n_envs, CAP(), stream, err, c, P);
+            if (rc == 0) note_launch(false, NL, CAP(), 0, P.phase_cycles != nullptr, false, P.out.obs_pre || P.out.state_pre, false, false, P.n_envs);
+            return rc;
+        });
     }
     // the kernel's view of the action source: the pool / table row of the launch's first tick, P.actions = that tick's actions of the
     // pool, the exploration noise (a variant without the actor receives the RolloutArgs part)
@@ -1330,9 +1347,14 @@ struct Backend {
                 if (const char *g = PVE_KNOB("PVE_PERSISTENT_GRID")) { const long long v = atoll(g); if (v > 0) grid = v; }   // A/B knob
                 if (grid > items) grid = items;
             }
-            return launch(V::kernel(), grid, V::CAP, stream, err, c, P, Rk);
+            const int rc = launch(V::kernel(), grid, V::CAP, stream, err, c, P, Rk);
+            // (pve_debug_last_variant: V's own arguments -- what ran, not what a picker intended)
+            if (rc == 0) note_launch(V::GEO, family_of(c), V::CAP, V::WPE, V::PROF, V::ACT, V::TRAIN, V::IDT, V::PERS, grid);
+            return rc;
         }
     }
+    static int family_of(const Const &) { return NL; }
+    static int family_of(const GeoConst &g) { return g.lane_num; }
     // The axes of a configuration, and what rules a resident kernel out in both families: the A/B knobs, and for the closed loop
     // the exact-float32 actor (per-tick launches run it) and a queue without R.actor_actions, through which an intersection's
     // actions go from one item to the next
@@ -1356,7 +1378,8 @@ struct Backend {
         if (P.phase_cycles) {
             // pve_debug_phase_cycles armed.  The phase-cycle diagnostics exist for the default kernel only: every other variant (table,
             // actor, training outputs) answers "no resident kernel" and the caller falls back to per-tick launches, which record the
-            // cycles (256 slots: no diagnostics variant of the resident kernel either).  The queue form has none: the chunked launches
+            // cycles -- except for the table source, which has no per-tick form: pve_step_many refuses it with PVE_ERR_STATE while
+            // armed (256 slots: no diagnostics variant of the resident kernel either).  The queue form has none: the chunked launches
             // record the cycles (as the geo path does) -- except in `make trace`, whose per-item timestamps go where the cycles would
             if (v.act) return none;
             if (!v.pers) {
@@ -1433,7 +1456,9 @@ struct Backend {
         // (PROF: the diagnostics build, pve_debug_phase_cycles; FIX4: the 4-lane layout's far-conflict path is a kernel of its own)
         return with_cap<128>(cap, err, [&](auto CAP) {
             return with_flags([&](auto PROF, auto FIX4) {
-                return launch(k_tick_geo<CAP(), PROF(), FIX4()>, P.n_envs, CAP(), stream, err, g, P);
+                const int rc = launch(k_tick_geo<CAP(), PROF(), FIX4()>, P.n_envs, CAP(), stream, err, g, P);
+                if (rc == 0) note_launch(true, g.lane_num, CAP(), 0, PROF(), false, P.out.obs_pre || P.out.state_pre, false, false, P.n_envs);
+                return rc;
             }, P.phase_cycles != nullptr, g.lane_num == 4);
         });
     }

@@ -220,6 +220,30 @@ inline int fail(int code, const std::string &msg)
     return code;
 }
 
+// What a stepping call launched (pve_debug_last_variant; `pve_launch_variant` of include/pve_env_debug.h restated for the
+// translation units that do not read the extension header).  A backend notes every tick / roll-out launch WHERE IT LAUNCHES
+// (note_launch: the template arguments of the kernel, not what a picker intended); pve_capi.inc clears the note in front of a
+// stepping call and copies it into the handle behind it.  Per thread, like the error text: calls on one handle are not concurrent.
+struct LaunchVariant {
+    int32_t kind, family, capacity, waves_per_simd, prof, actor, train, table, persistent, geo, grid, launches, reserved[4];
+};
+inline LaunchVariant &launch_note()
+{
+    static thread_local LaunchVariant v;
+    return v;
+}
+inline void note_launch(bool geo, int family, int cap, int waves_per_simd, bool prof, bool actor, bool train, bool table, bool pers,
+                        long long grid)
+{
+    LaunchVariant &v = launch_note();
+    const int32_t n = v.launches + 1;
+    memset(&v, 0, sizeof(v));
+    v.family = family; v.capacity = cap; v.waves_per_simd = waves_per_simd;
+    v.prof = prof; v.actor = actor; v.train = train; v.table = table; v.persistent = pers; v.geo = geo;
+    v.grid = (int32_t)(grid > 0x7fffffffLL ? 0x7fffffffLL : grid);
+    v.launches = n;
+}
+
 }  // namespace pve
 
 struct pve_handle_s {
@@ -246,6 +270,7 @@ struct pve_handle_s {
     int stop_phase;                   // pve_debug_stop_phase (diagnostics), -1 = off
     unsigned q_done_base;             // persistent roll-out: items completed per intersection since pve_reset (cumulative)
     int last_launch_kind;             // PVE_LAUNCH_*: what the last stepping call launched (pve_debug_last_launch)
+    pve::LaunchVariant last_variant;  // ... and which kernel variant, as the backend noted it at the launch (pve_debug_last_variant)
     bool has_tactor, has_critic;      // pve_set_target_networks installed a target actor / a critic in the workspace
     pve::ActionNoise noise;           // pve_set_action_noise (sigma = 0: off); tick0 is filled in per launch
 };

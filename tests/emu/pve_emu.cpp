@@ -309,6 +309,7 @@ struct Backend {
     static int launch_tick(const Const &c, const Params &P, int cap, void *, std::string &)
     {
         if (cap == 64) emu_tick<64>(c, P); else emu_tick<128>(c, P);
+        note_launch(false, NL, cap, 0, false, false, P.out.obs_pre || P.out.state_pre, false, false, 0);
         return 0;
     }
     // The persistent form (R.queue): the kernel's workgroups pull (intersection, chunk) items from a queue; here the items run
@@ -352,6 +353,8 @@ struct Backend {
             else if (home >= 2) emu_rollout<128, Shared<128, false, true, 296>>(cc, P, Rk, kb);
             else emu_rollout<128>(cc, P, Rk, kb); });
         if (rc < 0) err = "emulated work queue: inconsistent item schedule";
+        // (pve_debug_last_variant: what this backend knows -- no waves, no workgroups)
+        else note_launch(false, NL, cap, 0, false, false, P_in.out.obs_pre || P_in.out.state_pre, R.source == 3, R.queue != nullptr, 0);
         return rc;
     }
     static int launch_rollout_geo(const GeoConst &g, const Params &P_in, const RolloutArgs &R, int cap, void *, std::string &err)
@@ -361,6 +364,7 @@ struct Backend {
         const int rc = run_launch(g, P_in, R, cap, [&](const GeoConst &gg, const Params &P, const RolloutArgs &Rk, int kb) {
             if (cap == 64) emu_rollout_geo<64>(gg, P, Rk, kb); else emu_rollout_geo<128>(gg, P, Rk, kb); });
         if (rc < 0) err = "emulated work queue: inconsistent item schedule";
+        else note_launch(true, g.lane_num, cap, 0, false, false, train, R.source == 3, R.queue != nullptr, 0);
         return rc;
     }
     static int launch_compact(const Params &P, int cap, void *, std::string &)
@@ -371,6 +375,7 @@ struct Backend {
     static int launch_tick_geo(const GeoConst &g, const Params &P, int cap, void *, std::string &)
     {
         if (cap == 64) emu_tick_geo<64>(g, P); else emu_tick_geo<128>(g, P);
+        note_launch(true, g.lane_num, cap, 0, false, false, P.out.obs_pre || P.out.state_pre, false, false, 0);
         return 0;
     }
     static int launch_reset_geo(const GeoConst &g, const Params &P, int cap, void *, std::string &)

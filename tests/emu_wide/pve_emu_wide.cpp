@@ -169,6 +169,7 @@ struct Backend {
     static int launch_tick(const Const &c, const Params &P, int cap, void *, std::string &err)
     {
         if (by_cap(cap, [&](auto k) { emu_tick<decltype(k)::value>(c, P); }) != 0) { err = "no emulated tick for this capacity"; return -1; }
+        note_launch(false, NL, cap, 0, false, false, P.out.obs_pre || P.out.state_pre, false, false, 0);
         return 0;
     }
     // the persistent form (R.queue): the items run sequentially, chunk-major -- the item schedule of the kernel's queue
@@ -187,6 +188,7 @@ struct Backend {
             } else P.actions = nullptr;
             if (R.source == 3) Rk.pool_tick0 = R.pool_tick0 % R.n_pool;
             if (emu(P, Rk, 0) != 0) { err = "no emulated roll-out for this capacity"; return -1; }
+            note_launch(false, NL, cap, 0, false, false, P_in.out.obs_pre || P_in.out.state_pre, R.source == 3, false, 0);
             return 0;
         }
         for (int chunk = 0; chunk < R.n_full + R.n_taper; chunk++) {
@@ -198,6 +200,7 @@ struct Backend {
             P.actions = R.source == 1 ? R.pool + (size_t)Rk.pool_tick0 * (size_t)P.n_envs * (size_t)cap : nullptr;
             if (emu(P, Rk, kb) != 0) { err = "no emulated roll-out for this capacity"; return -1; }
         }
+        note_launch(false, NL, cap, 0, false, false, P_in.out.obs_pre || P_in.out.state_pre, R.source == 3, true, 0);
         return 0;
     }
     static int launch_compact(const Params &P, int cap, void *, std::string &err)

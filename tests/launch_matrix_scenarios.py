@@ -1,5 +1,5 @@
 """The launch matrix of pve_step_many: every combination of layout x capacity x action source x training outputs x launch
-form the API accepts, each on a tiny batch.  A case asserts WHICH path ran (last_launch() against a literal table: a backend
+form the API accepts, each on a tiny batch.  A case asserts WHICH path ran (last_launch() and last_variant() against literal tables: a backend
 that picks a valid but wrong kernel variant, or quietly falls back, fails here) and holds every requested output and the final
 state bit-equal to the same ticks run one launch per tick.  Shared by the CPU file (the emulators, their own table) and the
 `-m gpu` file."""
@@ -74,6 +74,61 @@ def expected_gpu(c):
     return "tick" if c.actor_f32 else GPU_TABLE[(c.lane_num == 12, c.source, c.train, c.persistent)]
 
 
+# last_variant() on the GPU, as literals (never computed from the picker's rules), by the key of GPU_TABLE:
+# (waves_per_simd at 128 slots, waves_per_simd at every other capacity, actor, train, table).  5 = the HOME build of the queue
+# kernel: exactly 12 lanes, 128 slots, queue form, zero / pool / table, no training outputs.  4 = the register build.
+# The 4- / 8-lane closed loop with the training outputs through the queue runs as chunked launches of the resident kernel.
+GPU_VARIANTS = {
+    (True, "zero", False, False): (4, 4, 0, 0, 0), (True, "zero", False, True): (5, 4, 0, 0, 0),
+    (True, "zero", True, False): (4, 4, 0, 1, 0), (True, "zero", True, True): (4, 4, 0, 1, 0),
+    (True, "pool", False, False): (4, 4, 0, 0, 0), (True, "pool", False, True): (5, 4, 0, 0, 0),
+    (True, "pool", True, False): (4, 4, 0, 1, 0), (True, "pool", True, True): (4, 4, 0, 1, 0),
+    (True, "table", False, False): (4, 4, 0, 0, 1), (True, "table", False, True): (5, 4, 0, 0, 1),
+    (True, "table", True, False): (4, 4, 0, 1, 1), (True, "table", True, True): (4, 4, 0, 1, 1),
+    (True, "actor", False, False): (4, 4, 1, 0, 0), (True, "actor", False, True): (4, 4, 1, 0, 0),
+    (True, "actor", True, False): (4, 4, 1, 1, 0), (True, "actor", True, True): (4, 4, 1, 1, 0),
+    (False, "zero", False, False): (4, 4, 0, 0, 0), (False, "zero", False, True): (4, 4, 0, 0, 0),
+    (False, "zero", True, False): (4, 4, 0, 1, 0), (False, "zero", True, True): (4, 4, 0, 1, 0),
+    (False, "pool", False, False): (4, 4, 0, 0, 0), (False, "pool", False, True): (4, 4, 0, 0, 0),
+    (False, "pool", True, False): (4, 4, 0, 1, 0), (False, "pool", True, True): (4, 4, 0, 1, 0),
+    (False, "table", False, False): (4, 4, 0, 0, 1), (False, "table", False, True): (4, 4, 0, 0, 1),
+    (False, "actor", False, False): (4, 4, 1, 0, 0), (False, "actor", False, True): (4, 4, 1, 0, 0),
+    (False, "actor", True, False): (4, 4, 1, 1, 0), (False, "actor", True, True): (4, 4, 1, 1, 0),
+}
+# workgroups of a queue launch = N_ENVS x items per intersection = 5 x pve_debug_item_schedule(11, 4)[11] = 15 (far below what
+# the chip holds); launches of a call: 1 for the queue, 1 for the plain resident form (chunk = 0), ceil(11 / 4) = 3 where the
+# queue form was asked for and chunked launches ran, 11 per-tick launches (22 with the actor pass in front of each)
+QUEUE_GRID, CHUNKED_LAUNCHES = 15, 3
+
+
+def expected_gpu_variant(c):
+    """the whole record of last_variant() for a case on the GPU"""
+    kind = expected_gpu(c)
+    v = dict(kind=kind, family=c.lane_num, capacity=c.capacity, geo=int(c.lane_num != 12), prof=0, grid=N_ENVS)
+    if kind == "tick":           # (the exact float32 actor: an actor launch and a tick launch per tick)
+        v.update(waves_per_simd=0, actor=0, train=int(c.train), table=0, persistent=0, launches=2 * N_TICKS)
+        return v
+    w128, w, actor, train, table = GPU_VARIANTS[(c.lane_num == 12, c.source, c.train, c.persistent)]
+    v.update(waves_per_simd=w128 if c.capacity == 128 else w, actor=actor, train=train, table=table,
+             persistent=int(kind == "persistent"))
+    if kind == "persistent":
+        v.update(grid=QUEUE_GRID, launches=1)
+    else:
+        v.update(launches=CHUNKED_LAUNCHES if c.persistent else 1)
+    return v
+
+
+def expected_emulated_variant(c):
+    """what the emulators know of their own table: the kind, the layout, the capacity and the flags -- no waves, no workgroups, and
+    the actor source as per-tick launches"""
+    kind = expected_emulated(c)
+    v = dict(kind=kind, family=c.lane_num, capacity=c.capacity, geo=int(c.lane_num != 12), prof=0, actor=0, train=int(c.train),
+             table=int(c.source == "table" and kind != "tick"), persistent=int(kind == "persistent"), waves_per_simd=0, grid=0)
+    v["launches"] = {"tick": N_TICKS * (2 if c.source == "actor" else 1), "persistent": 1,
+                     "resident": CHUNKED_LAUNCHES if c.persistent else 1}[kind]
+    return v
+
+
 def expected_emulated(c):
     """The emulators run the actor source as per-tick launches; every other row is the GPU's."""
     return "tick" if c.source == "actor" else expected_gpu(c)
@@ -138,7 +193,7 @@ def _same_tick(c, o1, o2, one, obs2, what):
     return int(ctl.sum())
 
 
-def run_case(backend, c, want):
+def run_case(backend, c, want, want_variant=None):
     one, many, pool = _batches(backend, c)
 
     def single():
@@ -154,6 +209,13 @@ def run_case(backend, c, want):
     res = many.step_many(N_TICKS, source=c.source, trajectory=c.train, chunk=chunk, persistent=c.persistent)
     many.synchronize()
     assert many.last_launch() == want, "%s: launched as %r, expected %r" % (what, many.last_launch(), want)
+    if want_variant is not None:
+        got = many.last_variant()
+        assert got == want_variant, "%s: launched %r, expected %r" % (what, got, want_variant)
+        if want_variant["kind"] == "persistent" and backend == "hip":         # (the grid literal against the library's own schedule)
+            import ctypes as C
+            sched = (C.c_int32 * 12)()
+            assert many.lib.pve_debug_item_schedule(N_TICKS, CHUNK, sched) == 0 and N_ENVS * sched[11] == QUEUE_GRID == got["grid"]
     n_ctl = 0
     for k in range(N_TICKS):
         o1 = single()

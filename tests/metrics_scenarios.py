@@ -205,7 +205,7 @@ def check_zero(b, what, spawned0):
     assert all(v == 0 for v in m.values()), "%s: metrics after reset(): %r" % (what, m)
 
 
-def drive(b, ref, form, chunk=0, persistent=False, what="", launch=None):
+def drive(b, ref, form, chunk=0, persistent=False, what="", launch=None, waves=None):
     """Runs the scenario's segments on batch `b` in launch form `form` and compares metrics() with the accumulators at the end of
     every segment.  Returns ({entry: worst deviation / bar}, the final metrics() dict)."""
     spec = ref.spec
@@ -232,6 +232,9 @@ def drive(b, ref, form, chunk=0, persistent=False, what="", launch=None):
             if launch is not None and not hasattr(b, "subs"):
                 want = launch if (0 < chunk < n or launch == "resident") else "resident"
                 assert b.last_launch() == want, (what, n, b.last_launch(), want)
+                if waves is not None:         # (the build a queue launch must be: 5 = HOME, 4 = the register build, as every other launch)
+                    v = b.last_variant()
+                    assert v["waves_per_simd"] == (waves if want == "persistent" else 4) and v["prof"] == 0, (what, n, v, waves)
         b.synchronize()
         t += n
         m = b.metrics()
@@ -242,14 +245,14 @@ def drive(b, ref, form, chunk=0, persistent=False, what="", launch=None):
 
 
 def check_open_loop(backend, name, form, outputs=OUTS, obs_dtype=torch.float64, chunk=0, persistent=False, launch=None,
-                    pipelined=0, replay=False):
+                    pipelined=0, replay=False, waves=None):
     """One scenario in one launch form against the accumulators.  replay=True: reset() then returns every entry to zero and the
     same run gives the same vector again, bit for bit in the float sums."""
     ref = reference(name)
     b = new_batch(ref, backend, outputs=outputs, obs_dtype=obs_dtype, pipelined=pipelined)
     what = "chunk %d%s" % (chunk, ", queue" if persistent else "")
     check_zero(b, what, ref.spawned0)
-    worst, m = drive(b, ref, form, chunk, persistent, what, launch)
+    worst, m = drive(b, ref, form, chunk, persistent, what, launch, waves)
     if replay:
         b.reset()
         check_zero(b, what + ", second reset", ref.spawned0)

@@ -508,11 +508,13 @@ def check_pipelined_equals_single(backend, n_envs=7, n_sub=3, capacity=128, tick
 
 
 def check_step_many(backend, source, n_envs=5, capacity=128, seed=71, chunks=(1, 7, 40, 3, 60), rate=1100.0,
-                    prefill=0, trajectory_chunk=12, arrivals=None, persistent=False, cfg=None, act_lo=-3.0, act_hi=3.0):
+                    prefill=0, trajectory_chunk=12, arrivals=None, persistent=False, cfg=None, act_lo=-3.0, act_hi=3.0, waves=None):
     """pve_step_many (n ticks per call, action source on the device) == n single-tick calls, bit for bit: persistent
     state, headers, observation rows, last-tick outputs and -- trajectory mode -- the outputs of every tick.
     persistent=True: the calls that are split into several chunks run as ONE launch whose workgroups pull (intersection,
-    chunk) items from the work queue (pve_rollout.persistent)."""
+    chunk) items from the work queue (pve_rollout.persistent).
+    waves: the build the queue launches must be (last_variant()["waves_per_simd"]: 5 = HOME, 4 = the register build; every
+    launch that is not a queue launch is a register build)."""
     from pve_mcc_amd._capi import PveError
     n_pool = 5
     rng = np.random.default_rng(seed)
@@ -568,6 +570,9 @@ def check_step_many(backend, source, n_envs=5, capacity=128, seed=71, chunks=(1,
         want = "persistent" if (persistent and ch > 0 and n > ch and not (backend == "emu" and source == "actor")) else \
             ("tick" if (backend == "emu" and source == "actor") else "resident")
         assert many.last_launch() == want, (many.last_launch(), want, source, n)
+        if waves is not None:
+            v = many.last_variant()
+            assert v["waves_per_simd"] == (waves if want == "persistent" else 4) and v["prof"] == 0, (v, waves, source, n)
         batches_equal(one, many, "%s, chunk of %d" % (source, n))
         same_outputs(o1, o2, "%s, chunk of %d" % (source, n))
     # trajectory mode: every tick's outputs
@@ -1013,7 +1018,7 @@ def check_full_size_vs_oracle(backend, n_envs, capacity, rate, ticks=420, n_samp
 
 def check_driver_shape_vs_oracle(backend, n_envs=4096, n_sub=2, capacity=128, rate=1100.0, chunk=5, n_sample=16,
                                  calls=(50, 50, 50, 50, 50, 50, 5, 20), n_pool=16, seed=20250213, trajectory=False, persistent=False,
-                                 table=False):
+                                 table=False, waves=None):
     """Exactly the launch shape the driver's `bench.py --steps 20 --warmup 5` runs:
     PipelinedIntersections, `n_sub` sub-batches on their own streams, pve_step_many calls of 50 (prefill) / 5 (warm-up) /
     20 (timed) ticks split into launches of `chunk` ticks, action pool of 16 slot-indexed entries.  `n_sample` envs spread
@@ -1074,6 +1079,10 @@ def check_driver_shape_vs_oracle(backend, n_envs=4096, n_sub=2, capacity=128, ra
         else:
             pipe.step_many(n, source=src, chunk=chunk, persistent=persistent)
         pipe.synchronize()
+        if waves is not None:                 # (the build every sub-batch's queue launch must be; any other launch: the register build)
+            for v in pipe.last_variant():
+                assert v["waves_per_simd"] == (waves if v["kind"] == "persistent" else 4) and v["kind"] != "tick", (v, waves, n)
+            assert not persistent or n <= chunk or all(k == "persistent" for k in pipe.last_launch())
         for e in sample:
             k, le = pipe.sub_of(e)
             o = oracles[e]

@@ -22,7 +22,7 @@ FULL = dict(source="table", seed=191, rate=3000.0, cfg=dict(vm=3.0, collision_th
 
 def run(backend, shape, n_envs):
     """check_step_many through the work queue; the metrics plus `mean_ctl` = controlled vehicles per intersection and tick"""
-    st = scenarios.check_step_many(backend, n_envs=n_envs, persistent=True, **shape)
+    st = scenarios.check_step_many(backend, n_envs=n_envs, persistent=True, waves=5 if backend == "hip" else None, **shape)
     st["mean_ctl"] = st["ctl_steps"] / st["ticks"]
     return st
 
@@ -41,4 +41,6 @@ def controlled_per_tick(backend, shape, n_envs):
     traj = b.step_many(ticks, source="table", trajectory=True, chunk=ticks // 3 + 1, persistent=True)
     b.synchronize()
     assert b.last_launch() == "persistent", b.last_launch()
+    if backend == "hip":                                    # (the side jobs live in the HOME build)
+        assert b.last_variant()["waves_per_simd"] == 5, b.last_variant()
     return _np(traj["env_out"])[:, :, 1]

@@ -160,3 +160,82 @@ def test_item_schedule_of_the_persistent_call_has_no_tiny_items():
                 assert min(items) >= 2, (K, T, items)
     out = (C.c_int32 * 12)()
     assert lib.pve_debug_item_schedule(10, 10, out) == -1 and lib.pve_debug_item_schedule(10, 0, out) == -1
+
+
+def test_debug_extension_header_and_launch_record():
+    """include/pve_env_debug.h: the record's layout against the binding, exactly EXPORTS_DEBUG declared, disjoint from the other
+    tuples (which keep their counts), exported by the product library and by the emulator"""
+    ext = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pve_env_debug.h")).read(), flags=re.S)
+    assert sorted(set(re.findall(r"\b(pve_[a-z_]+)\s*\(", ext))) == sorted(_capi.EXPORTS_DEBUG) == ["pve_debug_last_variant"]
+    body = re.search(r"typedef struct pve_launch_variant \{(.*?)\} pve_launch_variant;", ext, flags=re.S).group(1)
+    fields = re.findall(r"int32_t\s+([a-z_]+)(?:\[(\d+)\])?;", body)
+    assert [n for n, _ in fields] == [n for n, _ in _capi.PveLaunchVariant._fields_]
+    assert C.sizeof(_capi.PveLaunchVariant) == 4 * sum(int(k or 1) for _, k in fields) == 16 * 4
+    assert len(_capi.EXPORTS) == 44 and _capi.EXPORTS_EXT == ("pve_generate_arrivals",)
+    assert not set(_capi.EXPORTS_DEBUG) & set(_capi.EXPORTS + _capi.EXPORTS_EXT + _capi.EXPORTS_STATS)
+    main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pve_env.h")).read(), flags=re.S)
+    assert not any(n in main for n in _capi.EXPORTS_DEBUG)
+    import __graft_entry__
+    __graft_entry__.build()
+    assert all(hasattr(_capi.load_library(), n) and hasattr(emulator_lib(), n) for n in _capi.EXPORTS_DEBUG)
+
+
+def test_last_variant_and_probe_arguments_on_the_emulator():
+    """pve_debug_last_variant through the emulator build of the C ABI: zeros before the first call and after a call of zero ticks,
+    what the emulator knows of its launches otherwise; null arguments; pve_debug_traffic_probe's null sink"""
+    lib = emulator_lib()
+    arr = np.full((40, 12), np.inf)
+    arr[0, :] = 0.05
+    b = BatchedIntersections(2, 64, arr, device="cpu", outputs=("obs_post", "reward", "flags", "obs_pre"), _lib=lib)
+    b.reset()
+    none = dict(kind="none", family=0, capacity=0, waves_per_simd=0, prof=0, actor=0, train=0, table=0, persistent=0, geo=0, grid=0, launches=0)
+    assert b.last_variant() == none
+    v = _capi.PveLaunchVariant()
+    assert lib.pve_debug_last_variant(b._h, None) == -1 and b"pve_debug_last_variant" in lib.pve_last_error()
+    assert lib.pve_debug_last_variant(None, C.byref(v)) == -1
+    b.step(None)
+    tick = dict(none, kind="tick", family=12, capacity=64, train=1, launches=1)
+    assert b.last_variant() == tick and b.last_launch() == "tick"
+    b.step_many(5, source="zero")
+    assert b.last_variant() == dict(tick, kind="resident")
+    b.step_many(7, source="zero", chunk=3, persistent=True)
+    assert b.last_variant() == dict(tick, kind="persistent", persistent=1)
+    b.step_many(7, source="zero", chunk=3)
+    assert b.last_variant() == dict(tick, kind="resident", launches=3)
+    b.set_action_table(torch.zeros(4, 8, dtype=torch.float64))
+    b.step_many(4, source="table")
+    assert b.last_variant() == dict(tick, kind="resident", table=1)
+    b.step_many(0, source="zero")
+    assert b.last_variant() == none and b.last_launch() == "none"
+    w = torch.zeros(_capi.PVE_ACTOR_N_WEIGHTS, dtype=torch.float32)
+    b.set_actor(w)
+    b.step_with_actor()
+    assert b.last_variant() == dict(tick, launches=2)          # (the actor pass and the tick)
+    b.step_many(3, source="actor")
+    assert b.last_variant() == dict(tick, launches=6)
+    g = BatchedIntersections(2, 128, np.full((40, 8), np.inf), device="cpu", outputs=("obs_post", "flags"), lane_num=8, _lib=lib)
+    g.reset()
+    g.step_many(6, source="zero", chunk=2, persistent=True)
+    assert g.last_variant() == dict(none, kind="persistent", family=8, capacity=128, geo=1, persistent=1, launches=1)
+    assert lib.pve_debug_traffic_probe(b._h, None) == -1 and b"pve_debug_traffic_probe" in lib.pve_last_error()
+    assert lib.pve_debug_traffic_probe(None, C.c_void_p(w.data_ptr())) == -1
+
+
+def test_binding_dresses_a_library_older_than_the_debug_header():
+    """_capi._declare is also applied to libraries load_library has not vetted (the emulators): one built from sources older than
+    include/pve_env_debug.h gets every other signature and steps as before; only last_variant() refuses, and says why"""
+    real = emulator_lib()
+
+    class Older:
+        def __getattr__(self, name):
+            if name in _capi.EXPORTS_DEBUG:
+                raise AttributeError(name)
+            return getattr(real, name)
+
+    lib = _capi._declare(Older())
+    b = BatchedIntersections(2, 64, np.full((40, 12), np.inf), device="cpu", outputs=("obs_post", "flags"), _lib=lib)
+    b.reset()
+    b.step(None)
+    assert b.last_launch() == "tick"
+    with pytest.raises(_capi.PveError, match="pve_debug_last_variant"):
+        b.last_variant()

@@ -56,10 +56,11 @@ def _trajectory_in_items(source, capacity, full):
     for _ in range(prefill):
         single()
     many.step_many(prefill, source=source)                  # (one plain launch of the resident kernel)
-    assert many.last_launch() == "resident"
+    assert many.last_launch() == "resident" and many.last_variant()["waves_per_simd"] == 4
     scenarios.batches_equal(one, many, "after the prefill")
     traj = many.step_many(TICKS, source=source, trajectory=True, chunk=ITEM, persistent=True)
     assert many.last_launch() == "persistent"
+    assert many.last_variant()["waves_per_simd"] == (5 if capacity == 128 else 4)      # (128 slots: the HOME build)
     spawned = 0
     for k in range(TICKS):
         o1 = single()
@@ -92,4 +93,4 @@ def test_gpu_items_of_six_equal_single_ticks_full_intersection(source, capacity)
 def test_gpu_items_of_six_through_check_step_many(source):
     """the suite's own comparison (state, headers, rows, last-tick outputs, trajectory, metrics): calls of 17 ticks and a
     trajectory call of 11, both in items of 6"""
-    scenarios.check_step_many(BACKEND, source, n_envs=N_ENVS, chunks=(40, 17, 17), trajectory_chunk=11, seed=313, persistent=True)
+    scenarios.check_step_many(BACKEND, source, n_envs=N_ENVS, chunks=(40, 17, 17), trajectory_chunk=11, seed=313, persistent=True, waves=5)

@@ -13,7 +13,7 @@ BACKEND = "hip"
 
 @pytest.mark.parametrize("source", ["table", "pool", "zero"])
 def test_gpu_home_kernel_equals_single_ticks(source):
-    scenarios.check_step_many(BACKEND, source, n_envs=9, chunks=(20, 9, 33, 50), trajectory_chunk=14, seed=281, persistent=True)
+    scenarios.check_step_many(BACKEND, source, n_envs=9, chunks=(20, 9, 33, 50), trajectory_chunk=14, seed=281, persistent=True, waves=5)
 
 
 def test_gpu_home_kernel_full_intersection_multi_pass_and_late_spawn_gather():
@@ -21,7 +21,7 @@ def test_gpu_home_kernel_full_intersection_multi_pass_and_late_spawn_gather():
     304 list entries (several BUILD .. WALK passes: asserted on the emulator with the same streams' twin) and deferred spawns
     (overflow > 0: the table source gathers the spawned vehicle's first action behind FIN)."""
     st = scenarios.check_step_many(BACKEND, "table", n_envs=6, chunks=(250, 40, 7, 60), trajectory_chunk=10, seed=191, rate=3000.0,
-                                   cfg=dict(vm=3.0, collision_thr=0.01), act_lo=-3.0, act_hi=-2.0, persistent=True)
+                                   cfg=dict(vm=3.0, collision_thr=0.01), act_lo=-3.0, act_hi=-2.0, persistent=True, waves=5)
     assert st["max_alive"] >= 120 and st["overflow"] > 0, st
 
 
@@ -29,13 +29,13 @@ def test_gpu_table_source_late_spawn_gather_capacity_64():
     """the 8-workgroup kernels' late gather: 64 slots at a rate that fills them (queue form and plain launches)"""
     for pers in (True, False):
         st = scenarios.check_step_many(BACKEND, "table", n_envs=6, capacity=64, chunks=(200, 40, 7, 60), trajectory_chunk=10, seed=193,
-                                       rate=1500.0, cfg=dict(vm=3.0, collision_thr=0.01), act_lo=-3.0, act_hi=-2.0, persistent=pers)
+                                       rate=1500.0, cfg=dict(vm=3.0, collision_thr=0.01), act_lo=-3.0, act_hi=-2.0, persistent=pers, waves=4)
         assert st["overflow"] > 0, st
 
 
 def test_gpu_home_kernel_driver_shape_vs_oracle():
     m, _ = scenarios.check_driver_shape_vs_oracle(BACKEND, n_envs=512, n_sub=1, n_sample=8, calls=(50, 50, 50, 5, 20), chunk=12,
-                                                  persistent=True, table=True)
+                                                  persistent=True, table=True, waves=5)
     assert m["ctl_steps"] > 0
 
 
@@ -54,7 +54,7 @@ def test_gpu_home_kernel_items_of_one_and_two_ticks():
         for _ in range(n):
             one.step(one.actions_from_table())
         many.step_many(n, source="table", chunk=ch, persistent=True)
-        assert many.last_launch() == "persistent"
+        assert many.last_launch() == "persistent" and many.last_variant()["waves_per_simd"] == 5 and many.last_variant()["table"] == 1
         scenarios.batches_equal(one, many, "items of <= %d ticks" % ch)
 
 
@@ -75,4 +75,5 @@ def test_gpu_home_kernel_float32_observation_rows():
             one.step(pool[one.ticks % 5])
         many.step_many(n, source="pool", chunk=ch, persistent=True)
         assert many.last_launch() == "persistent" and many.obs.dtype == torch.float32
+        assert many.last_variant()["waves_per_simd"] == 5 and many.last_variant()["table"] == 0
         scenarios.batches_equal(one, many, "float32 rows, items of <= %d ticks" % ch)

@@ -10,7 +10,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("case", lm.matrix(), ids=lm.case_id)
 def test_gpu_launch_matrix(case):
-    lm.run_case("hip", case, lm.expected_gpu(case))
+    lm.run_case("hip", case, lm.expected_gpu(case), lm.expected_gpu_variant(case))
 
 
 @pytest.mark.parametrize("lane_num", [4, 8])

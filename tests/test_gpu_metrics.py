@@ -54,12 +54,12 @@ def test_gpu_rollout_metrics(name, kw):
 @pytest.mark.parametrize("chunk", [1, 7])
 def test_gpu_home_kernel_metrics(name, source, chunk):
     """the HOME build: the queue form at 128 slots"""
-    S.check_open_loop(BACKEND, name, source, chunk=chunk, **QUEUE)
+    S.check_open_loop(BACKEND, name, source, chunk=chunk, waves=5, **QUEUE)
 
 
 def test_gpu_rollout_metrics_register_build_128():
-    S.check_open_loop(BACKEND, "l12_c128", "pool", launch="resident")
-    S.check_open_loop(BACKEND, "l12_c128", "table", chunk=7, launch="resident")
+    S.check_open_loop(BACKEND, "l12_c128", "pool", launch="resident", waves=4)
+    S.check_open_loop(BACKEND, "l12_c128", "table", chunk=7, launch="resident", waves=4)
 
 
 @pytest.mark.parametrize("kw", [dict(launch="resident"), dict(chunk=7, **QUEUE)])

@@ -15,7 +15,22 @@ def test_launch_matrix_emulated(case, monkeypatch):
     if case.capacity == 256:
         lib = wide_lib()
         monkeypatch.setattr(hip_adapter, "emulator_lib", lambda: lib)
-    lm.run_case("emu", case, lm.expected_emulated(case))
+    lm.run_case("emu", case, lm.expected_emulated(case), lm.expected_emulated_variant(case))
+
+
+def test_variant_table_is_literal_and_home_holds_exactly_where_stated():
+    """the GPU table of variants: one row per row of the kind table; HOME (5) exactly for 12 lanes, 128 slots, the queue form,
+    zero / pool / table, no training outputs; the flags as requested; prof nowhere"""
+    assert set(lm.GPU_VARIANTS) == set(lm.GPU_TABLE)
+    home = [c for c in CASES if lm.expected_gpu_variant(c)["waves_per_simd"] == 5]
+    assert sorted(lm.case_id(c) for c in home) == ["l12-c128-pool-plain-queue-f32", "l12-c128-table-plain-queue-f64",
+                                                   "l12-c128-zero-plain-queue-f64"]
+    for c in CASES:
+        v = lm.expected_gpu_variant(c)
+        assert v["prof"] == 0 and v["kind"] == lm.expected_gpu(c)
+        if v["kind"] != "tick":
+            assert (v["table"], v["train"], v["actor"]) == (int(c.source == "table"), int(c.train), int(c.source == "actor")), c
+            assert v["waves_per_simd"] in (4, 5) and v["grid"] == (15 if v["kind"] == "persistent" else 5)
 
 
 def test_matrix_covers_every_accepted_combination():
