@@ -1,7 +1,7 @@
 // pve_capi.inc -- the extern "C" entry points of include/pve_env.h, written once against a
 // `Backend` (static interface) that the including translation unit defines before this file:
 //
-//   struct Backend {
+//   struct Backend : pve::BackendDefaults {
 //     static int   set_device(int dev, std::string &err);
 //     static int   enter_device(int dev);  static void leave_device(int prev);   // make dev current, return the previous one
 //     static void *dmalloc(size_t n);            static void dfree(void *p);
@@ -17,63 +17,22 @@
 //     static int   launch_rollout(const pve::Const &, const pve::Params &, const pve::RolloutArgs &, int cap, void *stream,
 //                                 std::string &err);    // 0 = launched, 1 = no resident kernel for this configuration, -1 = error
 //     static int   launch_rollout_geo(const pve::GeoConst &, const pve::Params &, const pve::RolloutArgs &, int cap, void *stream,
-//                                     std::string &err);
+//                                     std::string &err);    // (both: only a backend without the noisy launchers)
 //     static int   pack_actor(const float *W, float *flat, unsigned char *packed, void *stream, std::string &err);   // pve_set_actor
 //     static int   launch_actor(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
 //                               double *actions, int n_envs, int cap, void *stream, std::string &err);
-//     static constexpr int max_capacity = 256;   // optional: the largest capacity it runs (default 128, see backend_max_capacity)
-//     static int   launch_actor_noisy(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
-//                                     const int32_t *ids, const pve::ActionNoise &nz, double *actions, int n_envs, int cap,
-//                                     void *stream, std::string &err);
-//     static int   launch_rollout_noisy(const pve::Const &, const pve::Params &, const pve::RolloutArgs &, const pve::ActionNoise &,
-//                                       int cap, void *stream, std::string &err);
-//     static int   launch_rollout_geo_noisy(const pve::GeoConst &, const pve::Params &, const pve::RolloutArgs &,
-//                                           const pve::ActionNoise &, int cap, void *stream, std::string &err);
-//                                                // optional, all three or none: launch_actor / launch_rollout / launch_rollout_geo +
-//                                                // the exploration noise of pve_set_action_noise (ActionNoise::tick0 = first tick)
-//     static int   pack_target_networks(const float *actor_w, float *actor_flat, unsigned char *actor_packed, const float *critic_w,
-//                                       float *critic_flat, unsigned char *critic_packed, void *stream, std::string &err);
-//     static int   launch_critic(const unsigned char *critic_packed, const void *rows, int obs_f32, const float *act7, float *q,
-//                                long long n, void *stream, std::string &err);
-//     static int   launch_bootstrap_q(const unsigned char *actor_packed, const unsigned char *critic_packed, const void *state,
-//                                     int obs_f32, const int32_t *flags, float *q, float *act7_out, long long n, void *stream,
-//                                     std::string &err);
-//                                                // optional, all three or none: pve_set_target_networks / pve_critic_forward /
-//                                                // pve_bootstrap_q (a NULL weight pointer of pack_target_networks = keep that image)
-//     static int   launch_nstep_scan(const pve::NstepArgs &, int block_threads, void *stream, std::string &err);
-//     static int   launch_nstep_gather(const pve::NstepArgs &, void *stream, std::string &err);
-//                                                // optional, both or none: pve_nstep_scan / pve_nstep_gather (csrc/pve_nstep.h)
-//     static int   launch_replay_append(const pve::ReplayArgs &, const float *records, const long long *total_dev, long long n_max,
-//                                       int block_threads, void *stream, std::string &err);
-//     static int   launch_replay_sample(const pve::ReplayArgs &, long long batch, long long n_batches, float *rows, float *act7,
-//                                       float *target, long long *seq, int block_threads, void *stream, std::string &err);
-//                                                // optional, both or none: pve_replay_reset / _append / _sample (csrc/pve_replay.h)
-//     static int   launch_prio_reset(const pve::PrioArgs &, int block_threads, void *stream, std::string &err);
-//     static int   launch_prio_rank(const pve::PrioArgs &, int block_threads, void *stream, std::string &err);
-//     static int   launch_prio_sample(const pve::PrioArgs &, long long n_batches, long long min_live, float alpha_beta, float *rows,
-//                                     float *act7, float *target, long long *seq, int32_t *rank, float *weight, int block_threads,
-//                                     void *stream, std::string &err);          // ranks first
-//     static int   launch_prio_update(const pve::PrioArgs &, const long long *seq, const float *q, const float *target, long long n,
-//                                     int block_threads, void *stream, std::string &err);
-//                                                // optional, all four or none: pve_prio_reset / _rank / _sample / _update (csrc/pve_prio.h)
-//     static int   launch_generate_arrivals(const pve::ArrivalArgs &, int block_threads, void *stream, std::string &err);
-//                                                // optional: pve_generate_arrivals (csrc/pve_arrivals.h)
-//     static int   launch_rollout_stats(const pve::StatsArgs &, int block_threads, void *stream, std::string &err);
-//     static int   launch_metrics_groups(const pve::EnvHeader *, int n_envs, int cap, const int32_t *group, int n_groups, double *out,
-//                                        void *stream, std::string &err);
-//                                                // optional, both or none: pve_rollout_stats / pve_metrics_groups (csrc/pve_stats.h)
-//     static int   launch_learner_init(float *params, const float *actor, const float *critic, const float *target_actor,
-//                                      const float *target_critic, float beta1, float beta2, void *stream, std::string &err);
-//     static int   launch_learner_step(const pve::LearnCtx &, int block_threads, void *stream, std::string &err);
-//                                                // optional, both or none: pve_learner_init / pve_learner_step (csrc/pve_learn.h)
-//     static int   launch_learner_step_wide(const pve::LearnCtx &, float *work, int groups, int block_threads, void *stream,
-//                                           std::string &err);     // optional: pve_learner_step_wide (learn_steps_wide)
+//     static int   launch_probe(const pve::Params &, int cap, int32_t *sink, void *stream, std::string &err);   // pve_debug_traffic_probe
 //   };
 //
-// pve_hip.hip supplies the HIP backend (the product); tests/emu/pve_emu.cpp a host loop used only
-// by the CPU tests.
+// That is the mandatory part.  The optional part -- max_capacity and the launchers of the feature groups -- is declared, with
+// bodies that refuse, in pve::BackendDefaults (pve_host.h); pve::Provides says which groups a backend overrides.  This file calls
+// the mandatory part as Backend:: and the optional part as Opt:: (pve::Contract<Backend>: Backend itself, or, for a Backend that
+// does not derive from the defaults, Backend with the defaults beside it).
+// pve_hip.hip supplies the HIP backend (the product, every group); tests/emu and tests/emu_wide host loops used only by the CPU
+// tests (no group).
 
 using namespace pve;
+typedef Contract<Backend> Opt;
 
 #ifndef PVE_KNOB                 // (A/B knobs of the measurement tooling: compiled in with -DPVE_AB_KNOBS only, see pve_hip.hip)
 #define PVE_KNOB(name_) ((const char *)nullptr)
@@ -175,188 +134,39 @@ static void item_schedule(int K, int T, RolloutArgs &R)
     R.n_taper = n_taper;
 }
 
-// The largest capacity the backend has kernels for: Backend::max_capacity when it declares one, else 128.  256 slots exist for
-// the 12-lane fast path only (k_tick<256> / k_rollout<256, ..>); the 4- / 8-lane layouts and the general path stop at 128.
-template <class B, class = void> struct backend_max_capacity { static constexpr int value = 128; };
-template <class B> struct backend_max_capacity<B, decltype((void)B::max_capacity)> { static constexpr int value = B::max_capacity; };
+// 256 slots exist for the 12-lane fast path only (k_tick<256> / k_rollout<256, ..>), and only in a backend that says so; the
+// 4- / 8-lane layouts and the general path stop at 128.
 static bool capacity_known(int capacity)
 {
-    return capacity == 64 || capacity == 128 || (capacity == 256 && backend_max_capacity<Backend>::value >= 256);
+    return capacity == 64 || capacity == 128 || (capacity == 256 && Opt::max_capacity >= 256);
 }
 
-// Exploration noise (pve_set_action_noise) needs kernels that draw it: Backend::launch_actor_noisy / launch_rollout_noisy /
-// launch_rollout_geo_noisy (detected by the first).  A backend without them runs the actor as before and pve_set_action_noise
-// refuses sigma > 0.
-template <class B, class = void> struct backend_noise {
-    static constexpr bool value = false;
-    static int launch_actor(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta, const int32_t *,
-                            const ActionNoise &, double *actions, int n_envs, int cap, void *stream, std::string &err)
-    {
-        return B::launch_actor(flat, packed, obs, mode, meta, actions, n_envs, cap, stream, err);
-    }
-    static int launch_rollout(const Const &c, const Params &P, const RolloutArgs &R, const ActionNoise &, int cap, void *stream, std::string &err)
-    {
-        return B::launch_rollout(c, P, R, cap, stream, err);
-    }
-    static int launch_rollout_geo(const GeoConst &g, const Params &P, const RolloutArgs &R, const ActionNoise &, int cap, void *stream,
-                                  std::string &err)
-    {
-        return B::launch_rollout_geo(g, P, R, cap, stream, err);
-    }
-};
-template <class B> struct backend_noise<B, decltype((void)&B::launch_actor_noisy)> {
-    static constexpr bool value = true;
-    static int launch_actor(const float *flat, const unsigned char *packed, const void *obs, int mode, const int32_t *meta, const int32_t *ids,
-                            const ActionNoise &nz, double *actions, int n_envs, int cap, void *stream, std::string &err)
-    {
-        if (nz.sigma == 0) return B::launch_actor(flat, packed, obs, mode, meta, actions, n_envs, cap, stream, err);
-        return B::launch_actor_noisy(flat, packed, obs, mode, meta, ids, nz, actions, n_envs, cap, stream, err);
-    }
-    static int launch_rollout(const Const &c, const Params &P, const RolloutArgs &R, const ActionNoise &nz, int cap, void *stream, std::string &err)
-    {
-        return B::launch_rollout_noisy(c, P, R, nz, cap, stream, err);
-    }
-    static int launch_rollout_geo(const GeoConst &g, const Params &P, const RolloutArgs &R, const ActionNoise &nz, int cap, void *stream,
-                                  std::string &err)
-    {
-        return B::launch_rollout_geo_noisy(g, P, R, nz, cap, stream, err);
-    }
-};
-// The target networks (pve_set_target_networks / pve_critic_forward / pve_bootstrap_q) need the kernels of pve_critic.h:
-// Backend::pack_target_networks / launch_critic / launch_bootstrap_q (detected by the last).  A backend without them exports the
-// three entry points all the same; they validate their arguments and then refuse with PVE_ERR_INVALID.
-template <class B, class = void> struct backend_target_q {
-    static constexpr bool value = false;
-    static int pack(const float *, float *, unsigned char *, const float *, float *, unsigned char *, void *, std::string &) { return -1; }
-    static int critic(const unsigned char *, const void *, int, const float *, float *, long long, void *, std::string &) { return -1; }
-    static int bootstrap(const unsigned char *, const unsigned char *, const void *, int, const int32_t *, float *, float *, long long,
-                         void *, std::string &) { return -1; }
-};
-template <class B> struct backend_target_q<B, decltype((void)&B::launch_bootstrap_q)> {
-    static constexpr bool value = true;
-    static int pack(const float *aw, float *af, unsigned char *ap, const float *cw, float *cf, unsigned char *cp, void *stream,
-                    std::string &err) { return B::pack_target_networks(aw, af, ap, cw, cf, cp, stream, err); }
-    static int critic(const unsigned char *cp, const void *rows, int obs_f32, const float *act7, float *q, long long n, void *stream,
-                      std::string &err) { return B::launch_critic(cp, rows, obs_f32, act7, q, n, stream, err); }
-    static int bootstrap(const unsigned char *ap, const unsigned char *cp, const void *state, int obs_f32, const int32_t *flags, float *q,
-                         float *act7_out, long long n, void *stream, std::string &err)
-    {
-        return B::launch_bootstrap_q(ap, cp, state, obs_f32, flags, q, act7_out, n, stream, err);
-    }
-};
-// The n-step pass (pve_nstep_scan / pve_nstep_gather) needs the kernels of pve_nstep.h: Backend::launch_nstep_scan /
-// launch_nstep_gather (detected by the second).  A backend without them exports the entry points all the same; they validate
-// their arguments and then refuse with PVE_ERR_INVALID.
-template <class B, class = void> struct backend_nstep {
-    static constexpr bool value = false;
-    static int scan(const NstepArgs &, int, void *, std::string &) { return -1; }
-    static int gather(const NstepArgs &, void *, std::string &) { return -1; }
-};
-template <class B> struct backend_nstep<B, decltype((void)&B::launch_nstep_gather)> {
-    static constexpr bool value = true;
-    static int scan(const NstepArgs &A, int block, void *stream, std::string &err) { return B::launch_nstep_scan(A, block, stream, err); }
-    static int gather(const NstepArgs &A, void *stream, std::string &err) { return B::launch_nstep_gather(A, stream, err); }
-};
-// The replay memory (pve_replay_reset / pve_replay_append / pve_replay_sample) needs the kernels of pve_replay.h:
-// Backend::launch_replay_append / launch_replay_sample (detected by the second).  A backend without them exports the entry points
-// all the same; they validate their arguments and then refuse with PVE_ERR_INVALID.
-template <class B, class = void> struct backend_replay {
-    static constexpr bool value = false;
-    static int append(const ReplayArgs &, const float *, const long long *, long long, int, void *, std::string &) { return -1; }
-    static int sample(const ReplayArgs &, long long, long long, float *, float *, float *, long long *, int, void *, std::string &) { return -1; }
-};
-template <class B> struct backend_replay<B, decltype((void)&B::launch_replay_sample)> {
-    static constexpr bool value = true;
-    static int append(const ReplayArgs &A, const float *records, const long long *total_dev, long long n_max, int block, void *stream,
-                      std::string &err) { return B::launch_replay_append(A, records, total_dev, n_max, block, stream, err); }
-    static int sample(const ReplayArgs &A, long long batch, long long n_batches, float *rows, float *act7, float *target, long long *seq,
-                      int block, void *stream, std::string &err)
-    {
-        return B::launch_replay_sample(A, batch, n_batches, rows, act7, target, seq, block, stream, err);
-    }
-};
-// The prioritised memory (pve_prio_reset / _rank / _sample / _update) needs the kernels of pve_prio.h: Backend::launch_prio_reset /
-// launch_prio_rank / launch_prio_sample / launch_prio_update (detected by the third).  A backend without them exports the entry
-// points all the same; they validate their arguments and then refuse with PVE_ERR_INVALID.
-template <class B, class = void> struct backend_prio {
-    static constexpr bool value = false;
-    static int reset(const PrioArgs &, int, void *, std::string &) { return -1; }
-    static int rank(const PrioArgs &, int, void *, std::string &) { return -1; }
-    static int sample(const PrioArgs &, long long, long long, float, float *, float *, float *, long long *, int32_t *, float *, int, void *,
-                      std::string &) { return -1; }
-    static int update(const PrioArgs &, const long long *, const float *, const float *, long long, int, void *, std::string &) { return -1; }
-};
-template <class B> struct backend_prio<B, decltype((void)&B::launch_prio_sample)> {
-    static constexpr bool value = true;
-    static int reset(const PrioArgs &A, int block, void *stream, std::string &err) { return B::launch_prio_reset(A, block, stream, err); }
-    static int rank(const PrioArgs &A, int block, void *stream, std::string &err) { return B::launch_prio_rank(A, block, stream, err); }
-    static int sample(const PrioArgs &A, long long n_batches, long long min_live, float alpha_beta, float *rows, float *act7, float *target,
-                      long long *seq, int32_t *rank, float *weight, int block, void *stream, std::string &err)
-    {
-        return B::launch_prio_sample(A, n_batches, min_live, alpha_beta, rows, act7, target, seq, rank, weight, block, stream, err);
-    }
-    static int update(const PrioArgs &A, const long long *seq, const float *q, const float *target, long long n, int block, void *stream,
-                      std::string &err) { return B::launch_prio_update(A, seq, q, target, n, block, stream, err); }
-};
-// The arrival generator (pve_generate_arrivals) needs the kernels of pve_arrivals.h: Backend::launch_generate_arrivals.  A backend
-// without it exports the entry point all the same; it validates its arguments and then refuses with PVE_ERR_INVALID.
-template <class B, class = void> struct backend_arrivals {
-    static constexpr bool value = false;
-    static int generate(const ArrivalArgs &, int, void *, std::string &) { return -1; }
-};
-template <class B> struct backend_arrivals<B, decltype((void)&B::launch_generate_arrivals)> {
-    static constexpr bool value = true;
-    static int generate(const ArrivalArgs &A, int block, void *stream, std::string &err) { return B::launch_generate_arrivals(A, block, stream, err); }
-};
-// The statistics (pve_rollout_stats / pve_metrics_groups) need the kernels of pve_stats.h: Backend::launch_rollout_stats and
-// launch_metrics_groups (detected by the first).  A backend without them exports the entry points all the same; they validate
-// their arguments and then refuse with PVE_ERR_INVALID.
-template <class B, class = void> struct backend_stats {
-    static constexpr bool value = false;
-    static int rollout(const StatsArgs &, int, void *, std::string &) { return -1; }
-    static int metrics(const EnvHeader *, int, int, const int32_t *, int, double *, void *, std::string &) { return -1; }
-};
-template <class B> struct backend_stats<B, decltype((void)&B::launch_rollout_stats)> {
-    static constexpr bool value = true;
-    static int rollout(const StatsArgs &A, int block, void *stream, std::string &err) { return B::launch_rollout_stats(A, block, stream, err); }
-    static int metrics(const EnvHeader *hd, int n_envs, int cap, const int32_t *group, int n_groups, double *out, void *stream,
-                       std::string &err) { return B::launch_metrics_groups(hd, n_envs, cap, group, n_groups, out, stream, err); }
-};
-// The learner step (pve_learner_init / pve_learner_step) needs the kernels behind Backend::launch_learner_init /
-// launch_learner_step (detected by the second).  A backend without them exports the entry points all the same; they validate
-// their arguments and then refuse with PVE_ERR_INVALID.
-template <class B, class = void> struct backend_learner {
-    static constexpr bool value = false;
-    static int init(float *, const float *, const float *, const float *, const float *, float, float, void *, std::string &) { return -1; }
-    static int step(const LearnCtx &, int, void *, std::string &) { return -1; }
-};
-template <class B> struct backend_learner<B, decltype((void)&B::launch_learner_step)> {
-    static constexpr bool value = true;
-    static int init(float *P, const float *a, const float *c, const float *ta, const float *tc, float beta1, float beta2, void *stream,
-                    std::string &err) { return B::launch_learner_init(P, a, c, ta, tc, beta1, beta2, stream, err); }
-    static int step(const LearnCtx &C, int block, void *stream, std::string &err) { return B::launch_learner_step(C, block, stream, err); }
-};
-// The wide step (pve_learner_step_wide) likewise, behind Backend::launch_learner_step_wide.
-template <class B, class = void> struct backend_learner_wide {
-    static constexpr bool value = false;
-    static int step(const LearnCtx &, float *, int, int, void *, std::string &) { return -1; }
-};
-template <class B> struct backend_learner_wide<B, decltype((void)&B::launch_learner_step_wide)> {
-    static constexpr bool value = true;
-    static int step(const LearnCtx &C, float *work, int groups, int block, void *stream, std::string &err)
-    {
-        return B::launch_learner_step_wide(C, work, groups, block, stream, err);
-    }
-};
-static_assert(LEARN_SLICE == PVE_LEARN_SLICE && LW_ROW == PVE_LEARNER_WIDE_ROW && LW_ROW % 4 == 0 &&
-              PVE_LEARNER_WIDE_FLOATS(1) == LW_ROW && PVE_LEARNER_WIDE_FLOATS(128) == LW_ROW && PVE_LEARNER_WIDE_FLOATS(129) == 2 * LW_ROW,
-              "the wide step's workspace (include/pve_env.h PVE_LEARNER_WIDE_*)");
-static_assert(LB_ACTOR == PVE_LEARNER_ACTOR && LB_CRITIC == PVE_LEARNER_CRITIC && LB_TACTOR == PVE_LEARNER_TARGET_ACTOR &&
-              LB_TCRITIC == PVE_LEARNER_TARGET_CRITIC && LB_M_ACTOR == PVE_LEARNER_M_ACTOR && LB_V_ACTOR == PVE_LEARNER_V_ACTOR &&
-              LB_M_CRITIC == PVE_LEARNER_M_CRITIC && LB_V_CRITIC == PVE_LEARNER_V_CRITIC && LB_POWERS == PVE_LEARNER_POWERS &&
-              LB_STEPS == PVE_LEARNER_STEPS && LB_GRAD == PVE_LEARNER_GRAD && LB_TOTAL == PVE_LEARNER_N_FLOATS &&
-              LRN_ACTOR_W == PVE_ACTOR_N_WEIGHTS && LRN_CRITIC_W == PVE_CRITIC_N_WEIGHTS && LEARN_CRITIC_ONLY == PVE_LEARN_CRITIC_ONLY,
-              "the learner's block layout (include/pve_env.h PVE_LEARNER_*)");
+// An optional group the backend does not provide (pve::Provides<Opt>): its entry points validate their arguments first
+static int no_kernels(const char *who, const char *what)
+{
+    return fail(PVE_ERR_INVALID, std::string(who) + ": this backend has no " + what + " kernels");
+}
+
+// the handle's noise for a launch whose first action is applied at the handle's current tick
+static ActionNoise noise_now(pve_handle h)
+{
+    ActionNoise nz = h->noise;
+    nz.tick0 = (uint32_t)(unsigned long long)h->ticks_since_reset;
+    return nz;
+}
+// pve_step_many's launch of a chunk or of the whole call, with the handle's noise where the backend draws it (read by the actor
+// variants only; ticks_since_reset moves with every chunk).  A template only so that `if constexpr` discards the branch a backend
+// cannot compile: the HIP backend has the noisy launchers and no launch_rollout / launch_rollout_geo, the emulators the reverse.
+template <class B = Opt> static int launch_rollout(pve_handle h, const Params &P, const RolloutArgs &R, std::string &err)
+{
+    if constexpr (Provides<B>::noise) {
+        const ActionNoise nz = noise_now(h);
+        return h->geo ? B::launch_rollout_geo_noisy(h->g, P, R, nz, h->cap, h->stream, err)
+                      : B::launch_rollout_noisy(h->c, P, R, nz, h->cap, h->stream, err);
+    } else
+        return h->geo ? B::launch_rollout_geo(h->g, P, R, h->cap, h->stream, err) : B::launch_rollout(h->c, P, R, h->cap, h->stream, err);
+}
+
 extern "C" {
 
 int pve_abi_version(void) { return PVE_ABI_VERSION; }
@@ -384,8 +194,8 @@ int pve_create(const pve_config *cfg, int n_envs, int capacity, int device_id, v
         return fail(PVE_ERR_INVALID, "pve_create: lane_num must be 12, 8 or 4 (the 3-lane branch is broken upstream)");
     if (n_envs <= 0) return fail(PVE_ERR_INVALID, "pve_create: n_envs must be > 0");
     if (!capacity_known(capacity))
-        return fail(PVE_ERR_INVALID, backend_max_capacity<Backend>::value >= 256 ? "pve_create: capacity must be 64, 128 or 256"
-                                                                                  : "pve_create: capacity must be 64 or 128");
+        return fail(PVE_ERR_INVALID, Opt::max_capacity >= 256 ? "pve_create: capacity must be 64, 128 or 256"
+                                                              : "pve_create: capacity must be 64 or 128");
     if (capacity == 256 && (cfg->lane_num != 12 || (cfg->flags & PVE_CFG_GENERAL_PATH)))
         return fail(PVE_ERR_INVALID, "pve_create: capacity 256 needs lane_num 12 on the fast path (not the 4- / 8-lane layouts, "
                                      "not PVE_CFG_GENERAL_PATH)");
@@ -511,7 +321,7 @@ static int tick_params(pve_handle h, const double *actions, const pve_outputs *o
 // copies the note -- what the backend wrote where it launched -- into the handle behind every launch that succeeded
 static void clear_variant(pve_handle h)
 {
-    memset(&launch_note(), 0, sizeof(LaunchVariant));
+    memset(&launch_note(), 0, sizeof(pve_launch_variant));
     memset(&h->last_variant, 0, sizeof(h->last_variant));
 }
 static void commit_variant(pve_handle h)
@@ -573,19 +383,14 @@ int pve_scene_update(pve_handle h, const double *actions, const pve_outputs *out
 static float *actor_flat(pve_handle h) { return (float *)(h->ws + h->L.off_actor_flat); }
 static unsigned char *actor_packed(pve_handle h) { return (unsigned char *)(h->ws + h->L.off_actor_packed); }
 
-// the handle's noise for a launch whose first action is applied at the handle's current tick
-static ActionNoise noise_now(pve_handle h)
-{
-    ActionNoise nz = h->noise;
-    nz.tick0 = (uint32_t)(unsigned long long)h->ticks_since_reset;
-    return nz;
-}
 // the stand-alone actor pass obs -> actions, with the handle's noise
 static int run_actor(pve_handle h, const void *obs, double *actions, std::string &err)
 {
     const int32_t *meta = (const int32_t *)(h->ws + h->L.off_i32[I_META]), *ids = (const int32_t *)(h->ws + h->L.off_i32[I_ID]);
-    return backend_noise<Backend>::launch_actor(actor_flat(h), actor_packed(h), obs, actor_mode(h), meta, ids, noise_now(h), actions,
-                                                h->n_envs, h->cap, h->stream, err);
+    if (h->noise.sigma == 0)                       // (always, on a backend without the noisy kernels: pve_set_action_noise)
+        return Backend::launch_actor(actor_flat(h), actor_packed(h), obs, actor_mode(h), meta, actions, h->n_envs, h->cap, h->stream, err);
+    return Opt::launch_actor_noisy(actor_flat(h), actor_packed(h), obs, actor_mode(h), meta, ids, noise_now(h), actions, h->n_envs,
+                                   h->cap, h->stream, err);
 }
 
 int pve_set_actor(pve_handle h, const float *weights)
@@ -619,20 +424,15 @@ int pve_actor_forward(pve_handle h, const float *weights, const void *obs, doubl
     return PVE_OK;
 }
 
-static int no_target_kernels(const char *who)
-{
-    return fail(PVE_ERR_INVALID, std::string(who) + ": this backend has no critic / bootstrap kernels");
-}
-
 int pve_set_target_networks(pve_handle h, const float *target_actor, const float *critic)
 {
     if (!h || (!target_actor && !critic)) return fail(PVE_ERR_INVALID, "pve_set_target_networks: null argument (at least one network is needed)");
-    if (!backend_target_q<Backend>::value) return no_target_kernels("pve_set_target_networks");
+    if (!Provides<Opt>::target_q) return no_kernels("pve_set_target_networks", "critic / bootstrap");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_target_q<Backend>::pack(target_actor, (float *)(h->ws + h->L.off_tactor_flat), (unsigned char *)(h->ws + h->L.off_tactor_packed),
-                                        critic, (float *)(h->ws + h->L.off_critic_flat), (unsigned char *)(h->ws + h->L.off_critic_packed),
-                                        h->stream, err) != 0)
+    if (Opt::pack_target_networks(target_actor, (float *)(h->ws + h->L.off_tactor_flat), (unsigned char *)(h->ws + h->L.off_tactor_packed),
+                                  critic, (float *)(h->ws + h->L.off_critic_flat), (unsigned char *)(h->ws + h->L.off_critic_packed),
+                                  h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_set_target_networks: " + err);
     if (target_actor) h->has_tactor = true;
     if (critic) h->has_critic = true;
@@ -643,12 +443,12 @@ int pve_critic_forward(pve_handle h, const void *rows, const float *act7, float 
 {
     if (!h || !rows || !act7 || !q) return fail(PVE_ERR_INVALID, "pve_critic_forward: null argument");
     if (n <= 0) return fail(PVE_ERR_INVALID, "pve_critic_forward: n must be > 0");
-    if (!backend_target_q<Backend>::value) return no_target_kernels("pve_critic_forward");
+    if (!Provides<Opt>::target_q) return no_kernels("pve_critic_forward", "critic / bootstrap");
     if (!h->has_critic) return fail(PVE_ERR_STATE, "pve_critic_forward: no critic installed (pve_set_target_networks)");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_target_q<Backend>::critic((const unsigned char *)(h->ws + h->L.off_critic_packed), rows, actor_mode(h) & 1, act7, q,
-                                          (long long)n, h->stream, err) != 0)
+    if (Opt::launch_critic((const unsigned char *)(h->ws + h->L.off_critic_packed), rows, actor_mode(h) & 1, act7, q, (long long)n,
+                           h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_critic_forward: " + err);
     return PVE_OK;
 }
@@ -657,14 +457,14 @@ int pve_bootstrap_q(pve_handle h, const void *state, const int32_t *flags, float
 {
     if (!h || !state || !q) return fail(PVE_ERR_INVALID, "pve_bootstrap_q: null argument");
     if (n <= 0) return fail(PVE_ERR_INVALID, "pve_bootstrap_q: n must be > 0");
-    if (!backend_target_q<Backend>::value) return no_target_kernels("pve_bootstrap_q");
+    if (!Provides<Opt>::target_q) return no_kernels("pve_bootstrap_q", "critic / bootstrap");
     if (!h->has_tactor || !h->has_critic)
         return fail(PVE_ERR_STATE, "pve_bootstrap_q: needs a target actor and a critic (pve_set_target_networks)");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_target_q<Backend>::bootstrap((const unsigned char *)(h->ws + h->L.off_tactor_packed),
-                                             (const unsigned char *)(h->ws + h->L.off_critic_packed), state, actor_mode(h) & 1, flags, q,
-                                             act7_out, (long long)n, h->stream, err) != 0)
+    if (Opt::launch_bootstrap_q((const unsigned char *)(h->ws + h->L.off_tactor_packed),
+                                (const unsigned char *)(h->ws + h->L.off_critic_packed), state, actor_mode(h) & 1, flags, q, act7_out,
+                                (long long)n, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_bootstrap_q: " + err);
     return PVE_OK;
 }
@@ -706,7 +506,7 @@ static int nstep_args(pve_handle h, const pve_nstep *ns, bool gather, const char
     }
     A.obs_first = ns->obs_first; A.q_boot = ns->q_boot; A.target = ns->target; A.code = ns->code; A.offsets = ns->offsets;
     A.total = (long long *)ns->total; A.max_records = ns->max_records; A.records = ns->records; A.index = ns->index;
-    if (!backend_nstep<Backend>::value) return fail(PVE_ERR_INVALID, w + ": this backend has no n-step kernels");
+    if (!Provides<Opt>::nstep) return no_kernels(who, "n-step");
     return PVE_OK;
 }
 
@@ -717,7 +517,7 @@ int pve_nstep_scan(pve_handle h, const pve_nstep *ns)
     if (rc != PVE_OK) return rc;
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_nstep<Backend>::scan(A, ns->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_nstep_scan: " + err);
+    if (Opt::launch_nstep_scan(A, ns->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_nstep_scan: " + err);
     return PVE_OK;
 }
 
@@ -729,7 +529,7 @@ int pve_nstep_gather(pve_handle h, const pve_nstep *ns)
     if (A.max_records == 0) return PVE_OK;
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_nstep<Backend>::gather(A, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_nstep_gather: " + err);
+    if (Opt::launch_nstep_gather(A, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_nstep_gather: " + err);
     return PVE_OK;
 }
 
@@ -748,17 +548,12 @@ static int replay_args(pve_handle h, const pve_replay *rp, const char *who, Repl
     return PVE_OK;
 }
 
-static int no_replay_kernels(const char *who)
-{
-    return fail(PVE_ERR_INVALID, std::string(who) + ": this backend has no replay kernels");
-}
-
 int pve_replay_reset(pve_handle h, const pve_replay *rp)
 {
     ReplayArgs A;
     const int rc = replay_args(h, rp, "pve_replay_reset", A);
     if (rc != PVE_OK) return rc;
-    if (!backend_replay<Backend>::value) return no_replay_kernels("pve_replay_reset");
+    if (!Provides<Opt>::replay) return no_kernels("pve_replay_reset", "replay");
     DevScope dev_scope(h->device);
     if (Backend::memset0(A.state, sizeof(long long) * REPLAY_STATE_WORDS, h->stream) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_replay_reset: device memset failed");
@@ -774,11 +569,11 @@ int pve_replay_append(pve_handle h, const pve_replay *rp, const float *records, 
     if (n_max > 0 && !records) return fail(PVE_ERR_INVALID, "pve_replay_append: null records");
     if (((uintptr_t)records & 15) || ((uintptr_t)total_dev & 7))
         return fail(PVE_ERR_INVALID, "pve_replay_append: records must be 16-byte aligned, total_dev 8-byte aligned");
-    if (!backend_replay<Backend>::value) return no_replay_kernels("pve_replay_append");
+    if (!Provides<Opt>::replay) return no_kernels("pve_replay_append", "replay");
     if (n_max == 0) return PVE_OK;
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_replay<Backend>::append(A, records, (const long long *)total_dev, (long long)n_max, rp->block_threads, h->stream, err) != 0)
+    if (Opt::launch_replay_append(A, records, (const long long *)total_dev, (long long)n_max, rp->block_threads, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_replay_append: " + err);
     return PVE_OK;
 }
@@ -795,11 +590,11 @@ int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t
     if (!rows || !act7 || !target || !seq) return fail(PVE_ERR_INVALID, "pve_replay_sample: null output");
     if (((uintptr_t)rows & 15) || ((uintptr_t)act7 & 15) || ((uintptr_t)target & 3) || ((uintptr_t)seq & 7))
         return fail(PVE_ERR_INVALID, "pve_replay_sample: rows and act7 must be 16-byte aligned, seq 8-byte, target 4-byte aligned");
-    if (!backend_replay<Backend>::value) return no_replay_kernels("pve_replay_sample");
+    if (!Provides<Opt>::replay) return no_kernels("pve_replay_sample", "replay");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_replay<Backend>::sample(A, (long long)batch, (long long)n_batches, rows, act7, target, (long long *)seq, rp->block_threads,
-                                        h->stream, err) != 0)
+    if (Opt::launch_replay_sample(A, (long long)batch, (long long)n_batches, rows, act7, target, (long long *)seq, rp->block_threads,
+                                  h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_replay_sample: " + err);
     return PVE_OK;
 }
@@ -835,11 +630,6 @@ static int prio_args(pve_handle h, const pve_prio *pp, const char *who, PrioArgs
     return PVE_OK;
 }
 
-static int no_prio_kernels(const char *who)
-{
-    return fail(PVE_ERR_INVALID, std::string(who) + ": this backend has no prioritised replay kernels");
-}
-
 size_t pve_prio_scratch_bytes(int64_t capacity)
 {
     return capacity < 1 || capacity > 0x7fffffffLL ? 0 : prio_scratch_bytes(capacity);
@@ -850,10 +640,10 @@ int pve_prio_reset(pve_handle h, const pve_prio *pp)
     PrioArgs A;
     const int rc = prio_args(h, pp, "pve_prio_reset", A);
     if (rc != PVE_OK) return rc;
-    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_reset");
+    if (!Provides<Opt>::prio) return no_kernels("pve_prio_reset", "prioritised replay");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_prio<Backend>::reset(A, pp->replay.block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_prio_reset: " + err);
+    if (Opt::launch_prio_reset(A, pp->replay.block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_prio_reset: " + err);
     return PVE_OK;
 }
 
@@ -862,10 +652,10 @@ int pve_prio_rank(pve_handle h, const pve_prio *pp)
     PrioArgs A;
     const int rc = prio_args(h, pp, "pve_prio_rank", A);
     if (rc != PVE_OK) return rc;
-    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_rank");
+    if (!Provides<Opt>::prio) return no_kernels("pve_prio_rank", "prioritised replay");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_prio<Backend>::rank(A, pp->replay.block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_prio_rank: " + err);
+    if (Opt::launch_prio_rank(A, pp->replay.block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_prio_rank: " + err);
     return PVE_OK;
 }
 
@@ -884,11 +674,11 @@ int pve_prio_sample(pve_handle h, const pve_prio *pp, int64_t n_batches, int64_t
     if (((uintptr_t)rows & 15) || ((uintptr_t)act7 & 15) || ((uintptr_t)target & 3) || ((uintptr_t)seq & 7) || ((uintptr_t)rank & 3) ||
         ((uintptr_t)weight & 3))
         return fail(PVE_ERR_INVALID, "pve_prio_sample: rows and act7 must be 16-byte aligned, seq 8-byte, target, rank and weight 4-byte aligned");
-    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_sample");
+    if (!Provides<Opt>::prio) return no_kernels("pve_prio_sample", "prioritised replay");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_prio<Backend>::sample(A, (long long)n_batches, (long long)min_live, alpha_beta, rows, act7, target, (long long *)seq, rank, weight,
-                                      pp->replay.block_threads, h->stream, err) != 0)
+    if (Opt::launch_prio_sample(A, (long long)n_batches, (long long)min_live, alpha_beta, rows, act7, target, (long long *)seq, rank,
+                                weight, pp->replay.block_threads, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_prio_sample: " + err);
     return PVE_OK;
 }
@@ -902,10 +692,10 @@ int pve_prio_update(pve_handle h, const pve_prio *pp, const int64_t *seq, const 
     if (n > 0 && (!seq || !q)) return fail(PVE_ERR_INVALID, "pve_prio_update: null seq or q");
     if (((uintptr_t)seq & 7) || ((uintptr_t)q & 3) || ((uintptr_t)target & 3))
         return fail(PVE_ERR_INVALID, "pve_prio_update: seq must be 8-byte aligned, q and target 4-byte aligned");
-    if (!backend_prio<Backend>::value) return no_prio_kernels("pve_prio_update");
+    if (!Provides<Opt>::prio) return no_kernels("pve_prio_update", "prioritised replay");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_prio<Backend>::update(A, (const long long *)seq, q, target, (long long)n, pp->replay.block_threads, h->stream, err) != 0)
+    if (Opt::launch_prio_update(A, (const long long *)seq, q, target, (long long)n, pp->replay.block_threads, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_prio_update: " + err);
     return PVE_OK;
 }
@@ -941,11 +731,11 @@ int pve_learner_init(pve_handle h, const pve_learner *lrn, const float *actor, c
     if (!actor || !critic) return fail(PVE_ERR_INVALID, "pve_learner_init: null actor or critic");
     if (((uintptr_t)actor | (uintptr_t)critic | (uintptr_t)target_actor | (uintptr_t)target_critic) & 15)
         return fail(PVE_ERR_INVALID, "pve_learner_init: the networks must be 16-byte aligned");
-    if (!backend_learner<Backend>::value) return fail(PVE_ERR_INVALID, "pve_learner_init: this backend has no learner kernels");
+    if (!Provides<Opt>::learner) return no_kernels("pve_learner_init", "learner");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_learner<Backend>::init(lrn->params, actor, critic, target_actor ? target_actor : actor, target_critic ? target_critic : critic,
-                                       H.beta1, H.beta2, h->stream, err) != 0)
+    if (Opt::launch_learner_init(lrn->params, actor, critic, target_actor ? target_actor : actor,
+                                 target_critic ? target_critic : critic, H.beta1, H.beta2, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_learner_init: " + err);
     return PVE_OK;
 }
@@ -963,12 +753,12 @@ int pve_learner_step(pve_handle h, const pve_learner *lrn, const float *rows, co
         return fail(PVE_ERR_INVALID, "pve_learner_step: n_batches must be >= 1 and batch * n_batches <= 2^31 - 1");
     if (((uintptr_t)rows & 15) || (((uintptr_t)act7 | (uintptr_t)target | (uintptr_t)losses | (uintptr_t)grads) & 3))
         return fail(PVE_ERR_INVALID, "pve_learner_step: rows must be 16-byte aligned, act7, target, losses and grads 4-byte aligned");
-    if (!backend_learner<Backend>::value) return fail(PVE_ERR_INVALID, "pve_learner_step: this backend has no learner kernels");
+    if (!Provides<Opt>::learner) return no_kernels("pve_learner_step", "learner");
     C.P = lrn->params; C.rows = rows; C.act7 = act7; C.target = target; C.losses = losses; C.grads = grads;
     C.batch = (int)batch; C.n_batches = (int)n_batches;
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_learner<Backend>::step(C, lrn->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_learner_step: " + err);
+    if (Opt::launch_learner_step(C, lrn->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_learner_step: " + err);
     return PVE_OK;
 }
 
@@ -990,12 +780,12 @@ int pve_learner_step_wide(pve_handle h, const pve_learner *lrn, const float *row
     if (work_floats < (int64_t)PVE_LEARNER_WIDE_FLOATS(batch))
         return fail(PVE_ERR_INVALID, "pve_learner_step_wide: work_floats must be >= PVE_LEARNER_WIDE_FLOATS(batch)");
     if (groups < 0) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: groups must be >= 0");
-    if (!backend_learner_wide<Backend>::value) return fail(PVE_ERR_INVALID, "pve_learner_step_wide: this backend has no learner kernels");
+    if (!Provides<Opt>::learner_wide) return no_kernels("pve_learner_step_wide", "learner");
     C.P = lrn->params; C.rows = rows; C.act7 = act7; C.target = target; C.losses = losses; C.grads = grads;
     C.batch = (int)batch; C.n_batches = (int)n_batches;
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_learner_wide<Backend>::step(C, work, (int)groups, lrn->block_threads, h->stream, err) != 0)
+    if (Opt::launch_learner_step_wide(C, work, (int)groups, lrn->block_threads, h->stream, err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_learner_step_wide: " + err);
     return PVE_OK;
 }
@@ -1017,22 +807,18 @@ int pve_generate_arrivals(pve_handle h, const pve_arrival_gen *g, double *arriva
         return fail(PVE_ERR_INVALID, "pve_generate_arrivals: only lane_num = 8 draws intentions (ref :389-390)");
     if (((uintptr_t)arrivals & 15) || ((uintptr_t)intentions & 15) || ((uintptr_t)covered & 7) || ((uintptr_t)g->mean_env & 7))
         return fail(PVE_ERR_INVALID, "pve_generate_arrivals: arrivals and intentions must be 16-byte aligned, covered and mean_env 8-byte");
-    if (!backend_arrivals<Backend>::value) return fail(PVE_ERR_INVALID, "pve_generate_arrivals: this backend has no arrival generator kernels");
+    if (!Provides<Opt>::arrivals) return no_kernels("pve_generate_arrivals", "arrival generator");
     ArrivalArgs A;
     A.seed = g->seed; A.env_offset = (long long)g->env_offset; A.epoch = g->epoch; A.rows = g->rows; A.n_envs = h->n_envs;
     A.lane_num = h->lane_num; A.mean = g->mean_s; A.mean_env = g->mean_env; A.min_gap = g->min_gap_s; A.arrivals = arrivals;
     A.intentions = intentions; A.covered = covered;
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_arrivals<Backend>::generate(A, g->block_threads, h->stream, err) != 0)
-        return fail(PVE_ERR_NO_DEVICE, "pve_generate_arrivals: " + err);
+    if (Opt::launch_generate_arrivals(A, g->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_generate_arrivals: " + err);
     return PVE_OK;
 }
 
-// Roll-out and evaluation statistics (include/pve_env_stats.h; the definition is csrc/pve_stats.h).  `struct pve_stats` is the
-// public descriptor; this file reads it through its restatement StatsDesc (a translation unit that includes the public header
-// asserts that the two agree).
-struct pve_stats;
+// Roll-out and evaluation statistics (include/pve_env_stats.h; the definition is csrc/pve_stats.h)
 
 size_t pve_stats_scratch_bytes(int n_envs, int n_ticks)
 {
@@ -1040,9 +826,8 @@ size_t pve_stats_scratch_bytes(int n_envs, int n_ticks)
     return stats_scratch_bytes(n_envs, n_ticks);
 }
 
-int pve_rollout_stats(pve_handle h, const struct pve_stats *st)
+int pve_rollout_stats(pve_handle h, const pve_stats *d)
 {
-    const StatsDesc *d = (const StatsDesc *)st;
     if (!h || !d) return fail(PVE_ERR_INVALID, "pve_rollout_stats: null handle or descriptor");
     if (!d->flags || !d->reward || !d->env_out || !d->series || !d->scratch)
         return fail(PVE_ERR_INVALID, "pve_rollout_stats: null flags, reward, env_out, series or scratch");
@@ -1057,7 +842,7 @@ int pve_rollout_stats(pve_handle h, const struct pve_stats *st)
         ((uintptr_t)d->obs_pre & obs_mask) || ((uintptr_t)d->series & 7) || ((uintptr_t)d->totals & 7) || ((uintptr_t)d->scratch & 7))
         return fail(PVE_ERR_INVALID, "pve_rollout_stats: every block must be aligned to its element type");
     if (h->cap % STAT_LANES) return fail(PVE_ERR_INVALID, "pve_rollout_stats: the capacity must be a multiple of 64");
-    if (!backend_stats<Backend>::value) return fail(PVE_ERR_INVALID, "pve_rollout_stats: this backend has no statistics kernels");
+    if (!Provides<Opt>::stats) return no_kernels("pve_rollout_stats", "statistics");
     StatsArgs A;
     A.n_envs = h->n_envs; A.cap = h->cap; A.n_ticks = d->n_ticks; A.n_groups = d->n_groups;
     A.obs_f32 = (h->cfg.flags & PVE_CFG_OBS_F32) ? 1 : 0;
@@ -1065,8 +850,7 @@ int pve_rollout_stats(pve_handle h, const struct pve_stats *st)
     A.series = d->series; A.totals = d->totals; A.scratch = (double *)d->scratch;
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_stats<Backend>::rollout(A, d->block_threads, h->stream, err) != 0)
-        return fail(PVE_ERR_NO_DEVICE, "pve_rollout_stats: " + err);
+    if (Opt::launch_rollout_stats(A, d->block_threads, h->stream, err) != 0) return fail(PVE_ERR_NO_DEVICE, "pve_rollout_stats: " + err);
     return PVE_OK;
 }
 
@@ -1077,11 +861,11 @@ int pve_metrics_groups(pve_handle h, const int32_t *group, int n_groups, double 
         return fail(PVE_ERR_INVALID, "pve_metrics_groups: n_groups must be 1 .. 1024, and 1 without a group map");
     if (((uintptr_t)group & 3) || ((uintptr_t)out & 7))
         return fail(PVE_ERR_INVALID, "pve_metrics_groups: group must be 4-byte aligned, out 8-byte");
-    if (!backend_stats<Backend>::value) return fail(PVE_ERR_INVALID, "pve_metrics_groups: this backend has no statistics kernels");
+    if (!Provides<Opt>::stats) return no_kernels("pve_metrics_groups", "statistics");
     DevScope dev_scope(h->device);
     std::string err;
-    if (backend_stats<Backend>::metrics((const EnvHeader *)(h->ws + h->L.off_headers), h->n_envs, h->cap, group, n_groups, out, h->stream,
-                                        err) != 0)
+    if (Opt::launch_metrics_groups((const EnvHeader *)(h->ws + h->L.off_headers), h->n_envs, h->cap, group, n_groups, out, h->stream,
+                                   err) != 0)
         return fail(PVE_ERR_NO_DEVICE, "pve_metrics_groups: " + err);
     return PVE_OK;
 }
@@ -1091,7 +875,7 @@ int pve_set_action_noise(pve_handle h, double sigma, uint64_t seed, int64_t env_
     if (!h) return fail(PVE_ERR_INVALID, "pve_set_action_noise: null handle");
     if (!(sigma >= 0) || sigma > 1.7976931348623157e308)
         return fail(PVE_ERR_INVALID, "pve_set_action_noise: sigma must be finite and >= 0");
-    if (sigma > 0 && !backend_noise<Backend>::value)
+    if (sigma > 0 && !Provides<Opt>::noise)
         return fail(PVE_ERR_INVALID, "pve_set_action_noise: this backend has no noisy actor kernels (sigma must be 0)");
     h->noise.sigma = sigma; h->noise.seed = seed; h->noise.env_offset = env_offset;
     return PVE_OK;
@@ -1105,6 +889,19 @@ int pve_step_all_actor(pve_handle h, const float *weights, const void *obs_in, d
     int rc = pve_actor_forward(h, weights, obs_in, actions);
     if (rc != PVE_OK) return rc;
     return run_tick(h, actions, out, MODE_FUSED, "pve_step_all_actor", 1);
+}
+
+// What the queue form and the chunked form of pve_step_many hand a roll-out launch alike, for a launch that starts at tick k0 of
+// the call (everything else zero): the action source, and the rows the tick in front of the launch stored
+static void fill_rollout_args(pve_handle h, const pve_rollout *ro, int k0, const void *actor_obs, const void *prev_rows, RolloutArgs &R)
+{
+    memset(&R, 0, sizeof(R));
+    R.source = ro->source; R.pool = ro->pool; R.n_pool = ro->n_pool;
+    R.pool_tick0 = (ro->source == PVE_SRC_POOL || ro->source == PVE_SRC_TABLE) ? (int)(((long long)ro->pool_tick0 + k0) % ro->n_pool) : 0;
+    R.table_ids = ro->table_ids;
+    R.trajectory = ro->trajectory ? 1 : 0;
+    R.actor_packed = actor_packed(h); R.actor_obs = actor_obs;
+    R.prev_rows = prev_rows;
 }
 
 int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
@@ -1147,22 +944,14 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
         (ro->source == PVE_SRC_ZERO || ro->source == PVE_SRC_POOL || ro->source == PVE_SRC_TABLE ||
          (ro->source == PVE_SRC_ACTOR && !(actor_mode(h) & 2)))) {
         RolloutArgs R;
-        memset(&R, 0, sizeof(R));
+        fill_rollout_args(h, ro, 0, ro->actor_obs, o0.obs_prev_post, R);
         item_schedule(ro->n_ticks, ro->chunk_ticks, R);
-        const int K = ro->n_ticks;
-        R.call_ticks = K;
-        R.source = ro->source; R.pool = ro->pool; R.n_pool = ro->n_pool;
-        R.pool_tick0 = (ro->source == PVE_SRC_POOL || ro->source == PVE_SRC_TABLE) ? (int)((long long)ro->pool_tick0 % ro->n_pool) : 0;
-        R.table_ids = ro->table_ids;
-        R.trajectory = ro->trajectory ? 1 : 0;
-        R.actor_packed = actor_packed(h); R.actor_obs = ro->actor_obs; R.actor_actions = ro->actor_actions;
-        R.prev_rows = o0.obs_prev_post;
+        R.call_ticks = ro->n_ticks;
+        R.actor_actions = ro->actor_actions;
         R.queue = (unsigned *)(h->ws + h->L.off_queue);
         R.n_shards = Backend::n_xcc(h->device);
         R.done_base = h->q_done_base;
-        const ActionNoise nz = noise_now(h);       // (read by the actor variants only)
-        const int rr = h->geo ? backend_noise<Backend>::launch_rollout_geo(h->g, P, R, nz, h->cap, h->stream, err)
-                              : backend_noise<Backend>::launch_rollout(h->c, P, R, nz, h->cap, h->stream, err);
+        const int rr = launch_rollout(h, P, R, err);
         if (rr < 0) { (void)queue_reset(h); return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err); }
         if (rr == 0) {
             h->q_done_base += (unsigned)(R.n_full + R.n_taper);
@@ -1176,28 +965,16 @@ int pve_step_many(pve_handle h, const pve_rollout *ro, const pve_outputs *out)
     {
         const int chunk = ro->chunk_ticks > 0 ? ro->chunk_ticks : ro->n_ticks;
         for (int k0 = 0; k0 < ro->n_ticks; k0 += chunk) {
+            // the block of the tick before this launch: the rows its first tick's actor reads (the caller's in the first launch)
+            // and, with a trajectory, the stale neighbour rows of state_pre
+            Outputs prev = o0;
+            if (k0 > 0 && ro->trajectory) shift_outputs(prev, o0, k0 - 1, E, cap, f32);
             RolloutArgs R;
-            memset(&R, 0, sizeof(R));
+            fill_rollout_args(h, ro, k0, k0 > 0 ? prev.obs_post : ro->actor_obs, k0 > 0 && ro->trajectory ? prev.obs_post : o0.obs_prev_post, R);
             R.n_ticks = (ro->n_ticks - k0 < chunk) ? ro->n_ticks - k0 : chunk;
-            R.source = ro->source; R.pool = ro->pool; R.n_pool = ro->n_pool;
-            R.pool_tick0 = (ro->source == PVE_SRC_POOL || ro->source == PVE_SRC_TABLE) ? (int)(((long long)ro->pool_tick0 + k0) % ro->n_pool) : 0;
-            R.table_ids = ro->table_ids;
-            R.trajectory = ro->trajectory ? 1 : 0;
-            R.actor_packed = actor_packed(h);
-            // the rows the first tick of this launch reads: the caller's, then what the previous launch's last tick stored
-            R.actor_obs = ro->actor_obs;
-            if (k0 > 0) {
-                R.actor_obs = o0.obs_post;
-                if (ro->trajectory) { Outputs prev; shift_outputs(prev, o0, k0 - 1, E, cap, f32); R.actor_obs = prev.obs_post; }
-            }
             R.exact_f32 = (actor_mode(h) & 2) ? 1 : 0;
-            // the rows the tick before this launch stored (stale neighbour rows of state_pre)
-            R.prev_rows = o0.obs_prev_post;
-            if (k0 > 0 && ro->trajectory) { Outputs prev; shift_outputs(prev, o0, k0 - 1, E, cap, f32); R.prev_rows = prev.obs_post; }
             if (ro->trajectory) shift_outputs(P.out, o0, k0, E, cap, f32);
-            const ActionNoise nz = noise_now(h);   // (ticks_since_reset moves with every chunk; read by the actor variants only)
-            const int rr = h->geo ? backend_noise<Backend>::launch_rollout_geo(h->g, P, R, nz, h->cap, h->stream, err)
-                                  : backend_noise<Backend>::launch_rollout(h->c, P, R, nz, h->cap, h->stream, err);
+            const int rr = launch_rollout(h, P, R, err);
             if (rr < 0) return fail(PVE_ERR_NO_DEVICE, std::string(who) + ": " + err);
             if (rr > 0) {
                 if (ro->source == PVE_SRC_TABLE)        // (nothing was launched: state and tick count are as before the call)
@@ -1303,7 +1080,7 @@ int pve_read_vehicles(pve_handle h, int env, pve_vehicle *out, int max_n, int *n
     const int m = n < max_n ? n : max_n;
     const int cap = h->cap;
     DevScope dev_scope(h->device);
-    static_assert(backend_max_capacity<Backend>::value <= 256, "pve_read_vehicles: the slot rows below hold 256 slots");
+    static_assert(Opt::max_capacity <= 256, "pve_read_vehicles: the slot rows below hold 256 slots");
     double f[NF64][256];
     int32_t iv[NI32][256];
     if (h->n_envs == 1) {
@@ -1390,13 +1167,10 @@ int pve_debug_last_launch(pve_handle h)
     return h->last_launch_kind;
 }
 
-// `struct pve_launch_variant` (include/pve_env_debug.h) is read through its restatement LaunchVariant (pve_host.h), like pve_stats
-struct pve_launch_variant;
-
-int pve_debug_last_variant(pve_handle h, struct pve_launch_variant *out)
+int pve_debug_last_variant(pve_handle h, pve_launch_variant *out)
 {
     if (!h || !out) return fail(PVE_ERR_INVALID, "pve_debug_last_variant: null handle or out");
-    *(LaunchVariant *)out = h->last_variant;
+    *out = h->last_variant;
     return PVE_OK;
 }
 

@@ -15,9 +15,6 @@
 #include <new>
 
 #include "pve_host.h"
-#include "../../include/pve_env_arrivals.h"      // (holds the definition in this translation unit to the public prototype)
-#include "../../include/pve_env_stats.h"         // (the same for pve_rollout_stats / pve_metrics_groups and their descriptor)
-#include "../../include/pve_env_debug.h"         // (the same for pve_debug_last_variant and its record)
 #include "pve_tick_core.h"
 #include "pve_tick_geo.h"
 #include "pve_actor.h"
@@ -30,37 +27,6 @@
 #include "pve_learn.h"
 
 using namespace pve;
-
-// csrc/pve_stats.h restates the public descriptor and column numbers of include/pve_env_stats.h
-static_assert(sizeof(StatsDesc) == sizeof(pve_stats) && offsetof(StatsDesc, n_ticks) == offsetof(pve_stats, n_ticks) &&
-              offsetof(StatsDesc, n_groups) == offsetof(pve_stats, n_groups) && offsetof(StatsDesc, reserved) == offsetof(pve_stats, reserved) &&
-              offsetof(StatsDesc, group) == offsetof(pve_stats, group) &&
-              offsetof(StatsDesc, flags) == offsetof(pve_stats, flags) && offsetof(StatsDesc, reward) == offsetof(pve_stats, reward) &&
-              offsetof(StatsDesc, obs_pre) == offsetof(pve_stats, obs_pre) && offsetof(StatsDesc, env_out) == offsetof(pve_stats, env_out) &&
-              offsetof(StatsDesc, series) == offsetof(pve_stats, series) && offsetof(StatsDesc, totals) == offsetof(pve_stats, totals) &&
-              offsetof(StatsDesc, scratch) == offsetof(pve_stats, scratch) && offsetof(StatsDesc, block_threads) == offsetof(pve_stats, block_threads),
-              "pve_stats.h and pve_env_stats.h disagree on the descriptor");
-static_assert(STAT_N == PVE_STAT_N && STAT_MAX_GROUPS == PVE_STAT_MAX_GROUPS && STAT_N_METRICS == PVE_N_METRICS &&
-              (int)STAT_ENV_TICKS == PVE_STAT_ENV_TICKS && (int)STAT_ALIVE == PVE_STAT_ALIVE && (int)STAT_SPAWNED == PVE_STAT_SPAWNED &&
-              (int)STAT_FINISHED == PVE_STAT_FINISHED && (int)STAT_DELETED == PVE_STAT_DELETED && (int)STAT_COLLISIONS == PVE_STAT_COLLISIONS &&
-              (int)STAT_LOCK == PVE_STAT_LOCK && (int)STAT_CTL == PVE_STAT_CTL && (int)STAT_COLLIDED == PVE_STAT_COLLIDED &&
-              (int)STAT_DONE == PVE_STAT_DONE && (int)STAT_SUM_REWARD == PVE_STAT_SUM_REWARD &&
-              (int)STAT_SUM_REWARD_SQ == PVE_STAT_SUM_REWARD_SQ && (int)STAT_SUM_V == PVE_STAT_SUM_V && (int)STAT_SUM_A == PVE_STAT_SUM_A &&
-              STAT_F_CTL == PVE_F_CTL && STAT_F_DONE == PVE_F_DONE, "pve_stats.h and the public headers disagree on the columns");
-static_assert(((STAT_EO_OF_COLUMN >> 0) & 7) == PVE_EO_N_PRE && ((STAT_EO_OF_COLUMN >> 4) & 7) == PVE_EO_N_SPAWNED &&
-              ((STAT_EO_OF_COLUMN >> 8) & 7) == PVE_EO_N_FINISHED && ((STAT_EO_OF_COLUMN >> 12) & 7) == PVE_EO_N_DELETED &&
-              ((STAT_EO_OF_COLUMN >> 16) & 7) == PVE_EO_COLLISIONS && ((STAT_EO_OF_COLUMN >> 20) & 7) == PVE_EO_LOCK,
-              "pve_stats.h and pve_env.h disagree on env_out");
-
-// csrc/pve_host.h restates the record of include/pve_env_debug.h
-static_assert(sizeof(LaunchVariant) == sizeof(pve_launch_variant) && offsetof(LaunchVariant, kind) == offsetof(pve_launch_variant, kind) &&
-              offsetof(LaunchVariant, family) == offsetof(pve_launch_variant, family) && offsetof(LaunchVariant, capacity) == offsetof(pve_launch_variant, capacity) &&
-              offsetof(LaunchVariant, waves_per_simd) == offsetof(pve_launch_variant, waves_per_simd) && offsetof(LaunchVariant, prof) == offsetof(pve_launch_variant, prof) &&
-              offsetof(LaunchVariant, actor) == offsetof(pve_launch_variant, actor) && offsetof(LaunchVariant, train) == offsetof(pve_launch_variant, train) &&
-              offsetof(LaunchVariant, table) == offsetof(pve_launch_variant, table) && offsetof(LaunchVariant, persistent) == offsetof(pve_launch_variant, persistent) &&
-              offsetof(LaunchVariant, geo) == offsetof(pve_launch_variant, geo) && offsetof(LaunchVariant, grid) == offsetof(pve_launch_variant, grid) &&
-              offsetof(LaunchVariant, launches) == offsetof(pve_launch_variant, launches) && offsetof(LaunchVariant, reserved) == offsetof(pve_launch_variant, reserved),
-              "pve_host.h and pve_env_debug.h disagree on the launch record");
 
 // A/B knobs of the measurement tooling (tools/ab_launch_shapes.py, tools/gpu.sh): environment variables that switch launch
 // shapes.  Compiled in only with -DPVE_AB_KNOBS (`make knobs` -> build/libpveenv_knobs.so); the product library reads no
@@ -1231,7 +1197,7 @@ template <typename Q> static long long resident_workgroups(std::string &err)
     return (long long)nb * cus;
 }
 
-struct Backend {
+struct Backend : BackendDefaults {
     // the largest capacity pve_create accepts (pve_capi.inc): 256 slots for the 12-lane fast path
     static constexpr int max_capacity = 256;
     static int bad_cap(int cap, std::string &err)
@@ -1485,8 +1451,7 @@ struct Backend {
         memset(&off, 0, sizeof(off));
         return launch_actor_noisy(W, packed, obs, mode, meta, nullptr, off, actions, n_envs, cap, stream, err);
     }
-    // the actor pass + the exploration noise of pve_set_action_noise (ids = the [n_envs][cap] id field; read when nz.sigma != 0).
-    // (pve_capi.inc takes its presence for that of launch_rollout_noisy / launch_rollout_geo_noisy as well)
+    // the actor pass + the exploration noise of pve_set_action_noise (ids = the [n_envs][cap] id field; read when nz.sigma != 0)
     static int launch_actor_noisy(const float *W, const unsigned char *packed, const void *obs, int mode, const int32_t *meta,
                                   const int32_t *ids, const ActionNoise &nz, double *actions, int n_envs, int cap, void *stream,
                                   std::string &err)
@@ -1591,49 +1556,40 @@ struct Backend {
     {
         return launch(k_learner_init, (LB_TOTAL + 255) / 256, 256, stream, err, P, actor, critic, tactor, tcritic, beta1, beta2);
     }
-    static int launch_learner_step(const LearnCtx &C, int block_threads, void *stream, std::string &err)
+    // The three kernels that take LEARN_LDS_FLOATS of dynamic LDS get the function attribute once per device -> that device's CU
+    // count (cached), or -1 (err set)
+    static int learner_setup(std::string &err)
     {
-        constexpr size_t lds = sizeof(float) * LEARN_LDS_FLOATS;
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) { err = hip_err("hipGetDevice", e); return -1; }
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-                e = hipFuncSetAttribute((const void *)k_learner_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) { err = hip_err("hipFuncSetAttribute", e); return -1; }
-                if (dev >= 0 && dev < 64) attr_set[dev] = true;
-            }
-        }
-        const int block = block_threads > 0 ? block_threads : 1024;
-        hipLaunchKernelGGL(k_learner_step, dim3(1), dim3(block), lds, (hipStream_t)stream, C);
-        return check_launch(err);
-    }
-    // pve_learner_step_wide: four launches per minibatch (two with PVE_LEARN_CRITIC_ONLY), enqueued in order, no host
-    // synchronisation.  groups = 0: one workgroup per slice, at most one per CU.  The slice kernels take the same dynamic LDS as
-    // k_learner_step: the function attribute once per kernel and device.
-    static int launch_learner_step_wide(const LearnCtx &C, float *work, int groups, int block_threads, void *stream, std::string &err)
-    {
-        constexpr size_t lds = sizeof(float) * LEARN_LDS_FLOATS;
         static std::mutex mu;
         static int n_cu[64] = {};
         int dev = 0, cus = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) { err = hip_err("hipGetDevice", e); return -1; }
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            if (dev < 0 || dev >= 64 || !n_cu[dev]) {
-                e = hipFuncSetAttribute((const void *)k_learner_slice<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e == hipSuccess)
-                    e = hipFuncSetAttribute((const void *)k_learner_slice<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e != hipSuccess) { err = hip_err("hipFuncSetAttribute", e); return -1; }
-                e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-                if (e != hipSuccess || cus <= 0) { err = hip_err("hipDeviceGetAttribute", e); return -1; }
-                if (dev >= 0 && dev < 64) n_cu[dev] = cus;
-            } else cus = n_cu[dev];
+        std::lock_guard<std::mutex> lock(mu);
+        if (dev >= 0 && dev < 64 && n_cu[dev]) return n_cu[dev];
+        for (const void *k : {(const void *)k_learner_step, (const void *)k_learner_slice<true>, (const void *)k_learner_slice<false>}) {
+            e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * LEARN_LDS_FLOATS));
+            if (e != hipSuccess) { err = hip_err("hipFuncSetAttribute", e); return -1; }
         }
+        e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess || cus <= 0) { err = hip_err("hipDeviceGetAttribute", e); return -1; }
+        if (dev >= 0 && dev < 64) n_cu[dev] = cus;
+        return cus;
+    }
+    static int launch_learner_step(const LearnCtx &C, int block_threads, void *stream, std::string &err)
+    {
+        if (learner_setup(err) < 0) return -1;
+        const int block = block_threads > 0 ? block_threads : 1024;
+        hipLaunchKernelGGL(k_learner_step, dim3(1), dim3(block), sizeof(float) * LEARN_LDS_FLOATS, (hipStream_t)stream, C);
+        return check_launch(err);
+    }
+    // pve_learner_step_wide: four launches per minibatch (two with PVE_LEARN_CRITIC_ONLY), enqueued in order, no host
+    // synchronisation.  groups = 0: one workgroup per slice, at most one per CU.
+    static int launch_learner_step_wide(const LearnCtx &C, float *work, int groups, int block_threads, void *stream, std::string &err)
+    {
+        constexpr size_t lds = sizeof(float) * LEARN_LDS_FLOATS;
+        const int cus = learner_setup(err);
+        if (cus < 0) return -1;
         const int n_slices = learn_n_slices(C.batch), want = groups > 0 ? groups : cus;
         const int grid = n_slices < want ? n_slices : want, block = block_threads > 0 ? block_threads : 1024;
         const bool with_actor = !(C.H.flags & LEARN_CRITIC_ONLY);
@@ -1743,6 +1699,16 @@ struct Backend {
         return with_cap(cap, err, [&](auto CAP) { return launch(k_reset<CAP()>, (P.n_envs + 63) / 64, 64, stream, err, c, P, 200000); });
     }
 };
+// the product provides every optional group of the contract: a missing or misspelt launcher fails the build here
+static_assert(Provides<Backend>::noise, "the HIP backend overrides launch_actor_noisy, launch_rollout_noisy and launch_rollout_geo_noisy");
+static_assert(Provides<Backend>::target_q, "the HIP backend overrides pack_target_networks, launch_critic and launch_bootstrap_q");
+static_assert(Provides<Backend>::nstep, "the HIP backend overrides launch_nstep_scan and launch_nstep_gather");
+static_assert(Provides<Backend>::replay, "the HIP backend overrides launch_replay_append and launch_replay_sample");
+static_assert(Provides<Backend>::prio, "the HIP backend overrides launch_prio_reset, launch_prio_rank, launch_prio_sample and launch_prio_update");
+static_assert(Provides<Backend>::arrivals, "the HIP backend overrides launch_generate_arrivals");
+static_assert(Provides<Backend>::stats, "the HIP backend overrides launch_rollout_stats and launch_metrics_groups");
+static_assert(Provides<Backend>::learner, "the HIP backend overrides launch_learner_init and launch_learner_step");
+static_assert(Provides<Backend>::learner_wide, "the HIP backend overrides launch_learner_step_wide");
 
 #include "pve_capi.inc"
 #endif   // PVE_PROBE_ONE / PVE_PROBE_GEO

@@ -1,13 +1,17 @@
 // pve_host.h -- backend-independent host side of the C ABI (handle, constants, layout).
-// Included by pve_hip.hip (product, HIP backend) and by tests/emu/pve_emu.cpp (CPU test emulator).
+// Included by pve_hip.hip (product, HIP backend) and by the CPU test emulators (tests/emu, tests/emu_wide).
 #pragma once
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/pve_env.h"
+#include "../../include/pve_env_arrivals.h"
+#include "../../include/pve_env_stats.h"
+#include "../../include/pve_env_debug.h"
 #include "pve_types.h"
 #include "pve_nstep.h"
 #include "pve_replay.h"
@@ -22,6 +26,27 @@ namespace pve {
 static_assert(REPLAY_REC == NSTEP_REC && REPLAY_REC == PVE_NSTEP_RECORD, "pve_replay.h and pve_nstep.h / pve_env.h disagree on the record");
 static_assert(REPLAY_STATE_WORDS == PVE_REPLAY_STATE_WORDS, "pve_replay.h and pve_env.h disagree on the state block");
 static_assert(sizeof(long long) == sizeof(int64_t), "the state block is int64");
+// the specification headers are also built alone and do not read the public ones: their constants are held to them here
+static_assert(STAT_N == PVE_STAT_N && STAT_MAX_GROUPS == PVE_STAT_MAX_GROUPS && STAT_N_METRICS == PVE_N_METRICS &&
+              (int)STAT_ENV_TICKS == PVE_STAT_ENV_TICKS && (int)STAT_ALIVE == PVE_STAT_ALIVE && (int)STAT_SPAWNED == PVE_STAT_SPAWNED &&
+              (int)STAT_FINISHED == PVE_STAT_FINISHED && (int)STAT_DELETED == PVE_STAT_DELETED && (int)STAT_COLLISIONS == PVE_STAT_COLLISIONS &&
+              (int)STAT_LOCK == PVE_STAT_LOCK && (int)STAT_CTL == PVE_STAT_CTL && (int)STAT_COLLIDED == PVE_STAT_COLLIDED &&
+              (int)STAT_DONE == PVE_STAT_DONE && (int)STAT_SUM_REWARD == PVE_STAT_SUM_REWARD &&
+              (int)STAT_SUM_REWARD_SQ == PVE_STAT_SUM_REWARD_SQ && (int)STAT_SUM_V == PVE_STAT_SUM_V && (int)STAT_SUM_A == PVE_STAT_SUM_A &&
+              STAT_F_CTL == PVE_F_CTL && STAT_F_DONE == PVE_F_DONE, "pve_stats.h and the public headers disagree on the columns");
+static_assert(((STAT_EO_OF_COLUMN >> 0) & 7) == PVE_EO_N_PRE && ((STAT_EO_OF_COLUMN >> 4) & 7) == PVE_EO_N_SPAWNED &&
+              ((STAT_EO_OF_COLUMN >> 8) & 7) == PVE_EO_N_FINISHED && ((STAT_EO_OF_COLUMN >> 12) & 7) == PVE_EO_N_DELETED &&
+              ((STAT_EO_OF_COLUMN >> 16) & 7) == PVE_EO_COLLISIONS && ((STAT_EO_OF_COLUMN >> 20) & 7) == PVE_EO_LOCK,
+              "pve_stats.h and pve_env.h disagree on env_out");
+static_assert(LEARN_SLICE == PVE_LEARN_SLICE && LW_ROW == PVE_LEARNER_WIDE_ROW && LW_ROW % 4 == 0 &&
+              PVE_LEARNER_WIDE_FLOATS(1) == LW_ROW && PVE_LEARNER_WIDE_FLOATS(128) == LW_ROW && PVE_LEARNER_WIDE_FLOATS(129) == 2 * LW_ROW,
+              "the wide step's workspace (include/pve_env.h PVE_LEARNER_WIDE_*)");
+static_assert(LB_ACTOR == PVE_LEARNER_ACTOR && LB_CRITIC == PVE_LEARNER_CRITIC && LB_TACTOR == PVE_LEARNER_TARGET_ACTOR &&
+              LB_TCRITIC == PVE_LEARNER_TARGET_CRITIC && LB_M_ACTOR == PVE_LEARNER_M_ACTOR && LB_V_ACTOR == PVE_LEARNER_V_ACTOR &&
+              LB_M_CRITIC == PVE_LEARNER_M_CRITIC && LB_V_CRITIC == PVE_LEARNER_V_CRITIC && LB_POWERS == PVE_LEARNER_POWERS &&
+              LB_STEPS == PVE_LEARNER_STEPS && LB_GRAD == PVE_LEARNER_GRAD && LB_TOTAL == PVE_LEARNER_N_FLOATS &&
+              LRN_ACTOR_W == PVE_ACTOR_N_WEIGHTS && LRN_CRITIC_W == PVE_CRITIC_N_WEIGHTS && LEARN_CRITIC_ONLY == PVE_LEARN_CRITIC_ONLY,
+              "the learner's block layout (include/pve_env.h PVE_LEARNER_*)");
 
 // Geometry and limits exactly as the reference constructor derives them
 // (ref traffic_interaction_scene.py:21-45, :148-152, :153-166, :182-186; libm = CPython's math).
@@ -220,22 +245,19 @@ inline int fail(int code, const std::string &msg)
     return code;
 }
 
-// What a stepping call launched (pve_debug_last_variant; `pve_launch_variant` of include/pve_env_debug.h restated for the
-// translation units that do not read the extension header).  A backend notes every tick / roll-out launch WHERE IT LAUNCHES
-// (note_launch: the template arguments of the kernel, not what a picker intended); pve_capi.inc clears the note in front of a
-// stepping call and copies it into the handle behind it.  Per thread, like the error text: calls on one handle are not concurrent.
-struct LaunchVariant {
-    int32_t kind, family, capacity, waves_per_simd, prof, actor, train, table, persistent, geo, grid, launches, reserved[4];
-};
-inline LaunchVariant &launch_note()
+// What a stepping call launched (pve_debug_last_variant, include/pve_env_debug.h).  A backend notes every tick / roll-out launch
+// WHERE IT LAUNCHES (note_launch: the template arguments of the kernel, not what a picker intended); pve_capi.inc clears the note in
+// front of a stepping call and copies it into the handle behind it.  Per thread, like the error text: calls on one handle are not
+// concurrent.
+inline pve_launch_variant &launch_note()
 {
-    static thread_local LaunchVariant v;
+    static thread_local pve_launch_variant v;
     return v;
 }
 inline void note_launch(bool geo, int family, int cap, int waves_per_simd, bool prof, bool actor, bool train, bool table, bool pers,
                         long long grid)
 {
-    LaunchVariant &v = launch_note();
+    pve_launch_variant &v = launch_note();
     const int32_t n = v.launches + 1;
     memset(&v, 0, sizeof(v));
     v.family = family; v.capacity = cap; v.waves_per_simd = waves_per_simd;
@@ -243,6 +265,77 @@ inline void note_launch(bool geo, int family, int cap, int waves_per_simd, bool 
     v.grid = (int32_t)(grid > 0x7fffffffLL ? 0x7fffffffLL : grid);
     v.launches = n;
 }
+
+// THE OPTIONAL PART OF THE BACKEND CONTRACT (the mandatory part: the comment at the head of pve_capi.inc).  A backend derives from
+// BackendDefaults and overrides, group by group, the launchers it has kernels for; what it leaves alone refuses, and the entry
+// points of that group validate their arguments and then answer "this backend has no ... kernels" (Provides, below).
+struct BackendDefaults {
+    static constexpr int max_capacity = 128;   // the largest capacity it runs: 256 slots exist for the 12-lane fast path only
+    // all three or none: launch_actor / launch_rollout / launch_rollout_geo + the exploration noise of pve_set_action_noise
+    // (ActionNoise::tick0 = first tick; ids = the [n_envs][cap] id field).  A backend with them needs no launch_rollout[_geo].
+    static int launch_actor_noisy(const float *, const unsigned char *, const void *, int, const int32_t *, const int32_t *,
+                                  const ActionNoise &, double *, int, int, void *, std::string &) { return -1; }
+    static int launch_rollout_noisy(const Const &, const Params &, const RolloutArgs &, const ActionNoise &, int, void *, std::string &) { return -1; }
+    static int launch_rollout_geo_noisy(const GeoConst &, const Params &, const RolloutArgs &, const ActionNoise &, int, void *,
+                                        std::string &) { return -1; }
+    // all three or none: pve_set_target_networks / pve_critic_forward / pve_bootstrap_q (csrc/pve_critic.h; a NULL weight pointer
+    // of pack_target_networks = keep that image)
+    static int pack_target_networks(const float *, float *, unsigned char *, const float *, float *, unsigned char *, void *,
+                                    std::string &) { return -1; }
+    static int launch_critic(const unsigned char *, const void *, int, const float *, float *, long long, void *, std::string &) { return -1; }
+    static int launch_bootstrap_q(const unsigned char *, const unsigned char *, const void *, int, const int32_t *, float *, float *,
+                                  long long, void *, std::string &) { return -1; }
+    // both or none: pve_nstep_scan / pve_nstep_gather (csrc/pve_nstep.h)
+    static int launch_nstep_scan(const NstepArgs &, int, void *, std::string &) { return -1; }
+    static int launch_nstep_gather(const NstepArgs &, void *, std::string &) { return -1; }
+    // both or none: pve_replay_reset / _append / _sample (csrc/pve_replay.h)
+    static int launch_replay_append(const ReplayArgs &, const float *, const long long *, long long, int, void *, std::string &) { return -1; }
+    static int launch_replay_sample(const ReplayArgs &, long long, long long, float *, float *, float *, long long *, int, void *,
+                                    std::string &) { return -1; }
+    // all four or none: pve_prio_reset / _rank / _sample / _update (csrc/pve_prio.h); launch_prio_sample ranks first
+    static int launch_prio_reset(const PrioArgs &, int, void *, std::string &) { return -1; }
+    static int launch_prio_rank(const PrioArgs &, int, void *, std::string &) { return -1; }
+    static int launch_prio_sample(const PrioArgs &, long long, long long, float, float *, float *, float *, long long *, int32_t *, float *,
+                                  int, void *, std::string &) { return -1; }
+    static int launch_prio_update(const PrioArgs &, const long long *, const float *, const float *, long long, int, void *,
+                                  std::string &) { return -1; }
+    // pve_generate_arrivals (csrc/pve_arrivals.h)
+    static int launch_generate_arrivals(const ArrivalArgs &, int, void *, std::string &) { return -1; }
+    // both or none: pve_rollout_stats / pve_metrics_groups (csrc/pve_stats.h)
+    static int launch_rollout_stats(const StatsArgs &, int, void *, std::string &) { return -1; }
+    static int launch_metrics_groups(const EnvHeader *, int, int, const int32_t *, int, double *, void *, std::string &) { return -1; }
+    // both or none: pve_learner_init / pve_learner_step (csrc/pve_learn.h)
+    static int launch_learner_init(float *, const float *, const float *, const float *, const float *, float, float, void *,
+                                   std::string &) { return -1; }
+    static int launch_learner_step(const LearnCtx &, int, void *, std::string &) { return -1; }
+    // pve_learner_step_wide (learn_steps_wide)
+    static int launch_learner_step_wide(const LearnCtx &, float *, int, int, void *, std::string &) { return -1; }
+};
+
+// Does backend B provide an optional group: it overrides every launcher of it.  (An override with another signature hides the
+// default, and the comparison of the two pointer types does not compile.)
+#define PVE_OVERRIDES(f_) (&B::f_ != &BackendDefaults::f_)
+template <class B> struct Provides {
+    static constexpr bool noise = PVE_OVERRIDES(launch_actor_noisy) && PVE_OVERRIDES(launch_rollout_noisy) && PVE_OVERRIDES(launch_rollout_geo_noisy);
+    static constexpr bool target_q = PVE_OVERRIDES(pack_target_networks) && PVE_OVERRIDES(launch_critic) && PVE_OVERRIDES(launch_bootstrap_q);
+    static constexpr bool nstep = PVE_OVERRIDES(launch_nstep_scan) && PVE_OVERRIDES(launch_nstep_gather);
+    static constexpr bool replay = PVE_OVERRIDES(launch_replay_append) && PVE_OVERRIDES(launch_replay_sample);
+    static constexpr bool prio = PVE_OVERRIDES(launch_prio_reset) && PVE_OVERRIDES(launch_prio_rank) && PVE_OVERRIDES(launch_prio_sample) &&
+                                 PVE_OVERRIDES(launch_prio_update);
+    static constexpr bool arrivals = PVE_OVERRIDES(launch_generate_arrivals);
+    static constexpr bool stats = PVE_OVERRIDES(launch_rollout_stats) && PVE_OVERRIDES(launch_metrics_groups);
+    static constexpr bool learner = PVE_OVERRIDES(launch_learner_init) && PVE_OVERRIDES(launch_learner_step);
+    static constexpr bool learner_wide = PVE_OVERRIDES(launch_learner_step_wide);
+};
+#undef PVE_OVERRIDES
+
+// How pve_capi.inc reaches the optional part: through the backend itself where it derives from BackendDefaults.  A Backend that
+// does not (an emulator source older than BackendDefaults, built against this directory) has none of the optional launchers: it
+// gets the defaults beside it and keeps a max_capacity of its own where it declares one.  Nothing here knows a feature.
+template <class B, class = void> struct OwnCapacity { static constexpr int value = BackendDefaults::max_capacity; };
+template <class B> struct OwnCapacity<B, decltype((void)B::max_capacity)> { static constexpr int value = B::max_capacity; };
+template <class B> struct BesideDefaults : BackendDefaults, B { static constexpr int max_capacity = OwnCapacity<B>::value; };
+template <class B> using Contract = std::conditional_t<std::is_base_of<BackendDefaults, B>::value, B, BesideDefaults<B>>;
 
 }  // namespace pve
 
@@ -270,7 +363,7 @@ struct pve_handle_s {
     int stop_phase;                   // pve_debug_stop_phase (diagnostics), -1 = off
     unsigned q_done_base;             // persistent roll-out: items completed per intersection since pve_reset (cumulative)
     int last_launch_kind;             // PVE_LAUNCH_*: what the last stepping call launched (pve_debug_last_launch)
-    pve::LaunchVariant last_variant;  // ... and which kernel variant, as the backend noted it at the launch (pve_debug_last_variant)
+    pve_launch_variant last_variant;  // ... and which kernel variant, as the backend noted it at the launch (pve_debug_last_variant)
     bool has_tactor, has_critic;      // pve_set_target_networks installed a target actor / a critic in the workspace
     pve::ActionNoise noise;           // pve_set_action_noise (sigma = 0: off); tick0 is filled in per launch
 };

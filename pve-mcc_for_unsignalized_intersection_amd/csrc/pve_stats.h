@@ -67,18 +67,6 @@ constexpr unsigned STAT_EO_OF_COLUMN = 0x324560u;
 constexpr int STAT_LANES = 64;                              // width of tree64: slots per step of 1., environments per chunk of 2.
 constexpr int STAT_BATCH = 64;                              // chunks whose q[j] wait in LDS at a time (launch detail, never results)
 
-// The layout of `pve_stats` (include/pve_env_stats.h), restated for the translation units that do not read the public extension
-// header (pve_hip.hip, which does, holds the two to each other).
-struct StatsDesc {
-    int32_t n_ticks, n_groups, block_threads, reserved;
-    const int32_t *group, *flags;
-    const double *reward;
-    const void *obs_pre;
-    const int32_t *env_out;
-    double *series, *totals;
-    void *scratch;
-};
-
 struct StatsArgs {
     int n_envs, cap, n_ticks, n_groups, obs_f32;
     const int32_t *group;                                   // [n_envs] or null

@@ -296,7 +296,7 @@ template <int CAP> static void emu_compact(const Params &P)
     delete shp;
 }
 
-struct Backend {
+struct Backend : BackendDefaults {
     static int set_device(int, std::string &) { return 0; }
     static int enter_device(int) { return 0; }
     static void leave_device(int) {}

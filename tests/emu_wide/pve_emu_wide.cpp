@@ -155,7 +155,7 @@ template <class F> static int by_cap(int cap, F f)
     return 0;
 }
 
-struct Backend {
+struct Backend : BackendDefaults {
     static constexpr int max_capacity = 256;
     static int set_device(int, std::string &) { return 0; }
     static int enter_device(int) { return 0; }

@@ -10,4 +10,4 @@ SHIM_CXXFLAGS = -O2 -fPIC -std=c++17 -ffp-contract=off -fno-fast-math $(WARN)
 # Every target depends on every header of the product, whichever it includes today: a rebuild too many costs seconds, a
 # library older than a header it includes runs the tests on code that is no longer there (tests/test_native_build.py
 # holds this list to the compiler's -MM).
-PREREQS = $(wildcard $(CSRC)/*.h $(CSRC)/*.inc) ../../include/pve_env.h ../native.mk Makefile
+PREREQS = $(wildcard $(CSRC)/*.h $(CSRC)/*.inc) $(wildcard ../../include/*.h) ../native.mk Makefile

@@ -17,7 +17,8 @@ HOST = [(d, lib, lib) for d, lib in (
     ("emu", "libpveenv_emu.so"), ("emu_wide", "libpveenv_emu_wide.so"), ("emu_diag", "libpveenv_emu_diag.so"),
     ("noise_host", "libnoise_host.so"), ("critic_host", "libcritic_host.so"), ("nstep_host", "libnstep_host.so"),
     ("replay_host", "libreplay_host.so"), ("learner_host", "liblearner_host.so"), ("learner_host", "liblearner_host_sub.so"),
-    ("math_probe", "libpve_math_probe_host.so"))]
+    ("learner_wide_host", "liblearner_wide_host.so"), ("prio_host", "libprio_host.so"), ("arrivals_host", "libarrivals_host.so"),
+    ("stats_host", "libstats_host.so"), ("math_probe", "libpve_math_probe_host.so"))]
 # the device flavour of the probe is the same source: its headers are those of the host flavour (-x c++)
 CASES = HOST + [("math_probe", "libpve_math_probe_hip.so", "libpve_math_probe_host.so")]
 
