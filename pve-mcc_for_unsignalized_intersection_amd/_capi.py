@@ -10,25 +10,27 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libpveenv.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
-PVE_LANES = 12
-PVE_MAX_DIRS = 16
 DIR_NUM = {4: 12, 8: 16, 12: 12}     # virtual-lane lists per layout (ref :86, :132, :167)
-CFG_GENERAL_PATH = 0x1
-CFG_OBS_F32 = 0x2
-CFG_GEO_SCAN = 0x4
-CFG_ACTOR_F32 = 0x8
-PVE_OBS_WIDTH = 28
-PVE_NBR = 6
-PVE_N_METRICS = 12
-PVE_ENV_OUT_N = 8
-PVE_ACTOR_N_WEIGHTS = 6393
-PVE_CRITIC_N_WEIGHTS = 6841
+# Every integer macro and enumerator of include/*.h, once: an upper-case integer here is the header's name with or without its
+# PVE_ prefix, and position k of a name tuple is the enumerator PVE_EO_<NAME> / PVE_M_<NAME> / PVE_LAUNCH_<NAME> (and
+# PVE_STAT_<NAME>: stats.STAT_NAMES) of value k.  tests/test_binding_contract.py holds both directions to the headers.
+ABI_VERSION = 9
+PVE_OK, PVE_ERR_INVALID, PVE_ERR_NO_DEVICE, PVE_ERR_STATE, PVE_ERR_NOMEM = 0, -1, -2, -3, -4
+PVE_LANES, PVE_MAX_DIRS, PVE_OBS_WIDTH, PVE_NBR, PVE_STATE_ROWS, PVE_N_METRICS, PVE_ENV_OUT_N = 12, 16, 28, 6, 7, 12, 8
+CFG_GENERAL_PATH, CFG_OBS_F32, CFG_GEO_SCAN, CFG_ACTOR_F32 = 0x1, 0x2, 0x4, 0x8
+PVE_ACTOR_N_WEIGHTS, PVE_CRITIC_N_WEIGHTS = 6393, 6841
 NSTEP_TAIL, NSTEP_MAX_WINDOW, NSTEP_RECORD = 0x1, 16, 36
 REPLAY_STATE_WORDS = 4
 PRIO_STATE_WORDS, PRIO_PARTS = 4, 32
-LEARN_SLICE, LEARNER_WIDE_ROW = 128, 13244
-ABI_VERSION = 9
+# float offsets of the learner block's segments (pve_mcc_amd/learner.py)
+LEARNER_ACTOR, LEARNER_CRITIC, LEARNER_TARGET_ACTOR, LEARNER_TARGET_CRITIC = 0, 6396, 13240, 19636
+LEARNER_M_ACTOR, LEARNER_V_ACTOR, LEARNER_M_CRITIC, LEARNER_V_CRITIC = 26480, 32876, 39272, 46116
+LEARNER_POWERS, LEARNER_STEPS, LEARNER_GRAD, LEARNER_N_FLOATS = 52960, 52964, 52968, 66208
+LEARN_CRITIC_ONLY, LEARN_SLICE, LEARNER_WIDE_ROW = 0x1, 128, 13244
 SRC_ZERO, SRC_POOL, SRC_ACTOR, SRC_TABLE = 0, 1, 2, 3
+PVE_STAT_N, PVE_STAT_MAX_GROUPS = 14, 1024
+LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
+LAUNCH_NAMES = ("none", "tick", "resident", "persistent")                      # ... as batched.last_launch() reports them
 
 F_ALIVE, F_CTL, F_DONE, F_DELETED, F_FINISHED, F_LOCK = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 F_INTENT_SHIFT = 6
@@ -120,87 +122,80 @@ class PveEnvInfo(C.Structure):
                 ("intention_re", C.c_int32)]
 
 
-EXPORTS = ("pve_abi_version", "pve_last_error", "pve_default_config", "pve_workspace_bytes", "pve_create",
-           "pve_destroy", "pve_set_stream", "pve_set_arrivals", "pve_reset", "pve_step_all",
-           "pve_scene_update", "pve_compact", "pve_read_env", "pve_read_vehicles", "pve_get_metrics",
-           "pve_state_field", "pve_synchronize", "pve_debug_phase_cycles", "pve_actor_forward",
-           "pve_step_all_actor", "pve_debug_traffic_probe", "pve_set_intentions", "pve_step_many", "pve_set_actor",
-           "pve_debug_stop_phase", "pve_debug_last_launch", "pve_debug_item_schedule", "pve_set_action_noise",
-           "pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q", "pve_nstep_scan", "pve_nstep_gather",
-           "pve_replay_reset", "pve_replay_append", "pve_replay_sample", "pve_learner_init", "pve_learner_step",
-           "pve_learner_step_wide", "pve_prio_scratch_bytes", "pve_prio_reset", "pve_prio_rank", "pve_prio_sample", "pve_prio_update")
-# entry points declared in extension headers (include/pve_env_arrivals.h), added within ABI 9 behind include/pve_env.h's 44
-EXPORTS_EXT = ("pve_generate_arrivals",)
-# ... and in include/pve_env_stats.h: roll-out and evaluation statistics by group (csrc/pve_stats.h)
-EXPORTS_STATS = ("pve_stats_scratch_bytes", "pve_rollout_stats", "pve_metrics_groups")
-PVE_STAT_N, PVE_STAT_MAX_GROUPS = 14, 1024
-# ... and in include/pve_env_debug.h: which kernel variant the last stepping call launched
-EXPORTS_DEBUG = ("pve_debug_last_variant",)
-LAUNCH_NONE, LAUNCH_TICK, LAUNCH_RESIDENT, LAUNCH_PERSISTENT = 0, 1, 2, 3      # pve_debug_last_launch
+vp, cint, i32, i64, u64, f32, f64 = C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_float, C.c_double
+P = C.POINTER
+# THE TABLE of entry points, by the header that declares them: name -> (restype, argtypes).  _declare, load_library's missing-symbol
+# check and the EXPORTS* tuples are read from it; tests/test_binding_contract.py holds it (and the structures and constants
+# above) to the four headers with the C++ compiler.  A new entry point is one row here.
+PROTOTYPES = {
+    "pve_env.h": {
+        "pve_abi_version": (cint, []),
+        "pve_last_error": (C.c_char_p, []),
+        "pve_default_config": (None, [P(PveConfig)]),
+        "pve_workspace_bytes": (C.c_size_t, [cint, cint]),
+        "pve_create": (cint, [P(PveConfig), cint, cint, cint, vp, vp, P(vp)]),
+        "pve_destroy": (cint, [vp]),
+        "pve_set_stream": (cint, [vp, vp]),
+        "pve_set_arrivals": (cint, [vp, vp, cint, cint]),
+        "pve_reset": (cint, [vp]),
+        "pve_step_all": (cint, [vp, vp, P(PveOutputs)]),
+        "pve_scene_update": (cint, [vp, vp, P(PveOutputs)]),
+        "pve_compact": (cint, [vp, vp]),
+        "pve_read_env": (cint, [vp, cint, P(PveEnvInfo)]),
+        "pve_read_vehicles": (cint, [vp, cint, P(PveVehicle), cint, P(cint)]),
+        "pve_get_metrics": (cint, [vp, P(f64)]),
+        "pve_state_field": (cint, [vp, C.c_char_p, P(vp), P(cint)]),
+        "pve_synchronize": (cint, [vp]),
+        "pve_debug_phase_cycles": (cint, [vp, vp]),
+        "pve_actor_forward": (cint, [vp, vp, vp, vp]),
+        "pve_step_all_actor": (cint, [vp, vp, vp, vp, P(PveOutputs)]),
+        "pve_debug_traffic_probe": (cint, [vp, vp]),
+        "pve_set_intentions": (cint, [vp, vp, cint, cint]),
+        "pve_step_many": (cint, [vp, P(PveRollout), P(PveOutputs)]),
+        "pve_set_actor": (cint, [vp, vp]),
+        "pve_debug_stop_phase": (cint, [vp, cint]),
+        "pve_debug_last_launch": (cint, [vp]),
+        "pve_debug_item_schedule": (cint, [cint, cint, P(i32)]),
+        "pve_set_action_noise": (cint, [vp, f64, u64, i64]),
+        "pve_set_target_networks": (cint, [vp, vp, vp]),
+        "pve_critic_forward": (cint, [vp, vp, vp, vp, i64]),
+        "pve_bootstrap_q": (cint, [vp, vp, vp, vp, vp, i64]),
+        "pve_nstep_scan": (cint, [vp, P(PveNstep)]),
+        "pve_nstep_gather": (cint, [vp, P(PveNstep)]),
+        "pve_replay_reset": (cint, [vp, P(PveReplay)]),
+        "pve_replay_append": (cint, [vp, P(PveReplay), vp, vp, i64]),
+        "pve_replay_sample": (cint, [vp, P(PveReplay), i64, i64, vp, vp, vp, vp]),
+        "pve_learner_init": (cint, [vp, P(PveLearner), vp, vp, vp, vp]),
+        "pve_learner_step": (cint, [vp, P(PveLearner), vp, vp, vp, i64, i64, vp, vp]),
+        "pve_learner_step_wide": (cint, [vp, P(PveLearner), vp, vp, vp, i64, i64, vp, i64, i32, vp, vp]),
+        "pve_prio_scratch_bytes": (C.c_size_t, [i64]),
+        "pve_prio_reset": (cint, [vp, P(PvePrio)]),
+        "pve_prio_rank": (cint, [vp, P(PvePrio)]),
+        "pve_prio_sample": (cint, [vp, P(PvePrio), i64, i64, f32, vp, vp, vp, vp, vp, vp]),
+        "pve_prio_update": (cint, [vp, P(PvePrio), vp, vp, vp, i64]),
+    },
+    # extension headers: entry points added within ABI 9 behind pve_env.h's own
+    "pve_env_arrivals.h": {"pve_generate_arrivals": (cint, [vp, P(PveArrivalGen), vp, vp, vp])},
+    "pve_env_stats.h": {                           # roll-out and evaluation statistics by group (csrc/pve_stats.h)
+        "pve_stats_scratch_bytes": (C.c_size_t, [cint, cint]),
+        "pve_rollout_stats": (cint, [vp, P(PveStats)]),
+        "pve_metrics_groups": (cint, [vp, vp, cint, vp]),
+    },
+    # which kernel variant the last stepping call launched
+    "pve_env_debug.h": {"pve_debug_last_variant": (cint, [vp, P(PveLaunchVariant)])},
+}
+EXPORTS, EXPORTS_EXT, EXPORTS_STATS, EXPORTS_DEBUG = (tuple(PROTOTYPES[h]) for h in (
+    "pve_env.h", "pve_env_arrivals.h", "pve_env_stats.h", "pve_env_debug.h"))
 
 
 def _declare(L):
-    vp = C.c_void_p
-    L.pve_abi_version.restype = C.c_int
-    L.pve_last_error.restype = C.c_char_p
-    L.pve_default_config.argtypes = [C.POINTER(PveConfig)]
-    L.pve_workspace_bytes.restype = C.c_size_t
-    L.pve_workspace_bytes.argtypes = [C.c_int, C.c_int]
-    L.pve_create.argtypes = [C.POINTER(PveConfig), C.c_int, C.c_int, C.c_int, vp, vp, C.POINTER(vp)]
-    L.pve_destroy.argtypes = [vp]
-    L.pve_set_stream.argtypes = [vp, vp]
-    L.pve_set_arrivals.argtypes = [vp, vp, C.c_int, C.c_int]
-    L.pve_set_intentions.argtypes = [vp, vp, C.c_int, C.c_int]
-    L.pve_reset.argtypes = [vp]
-    L.pve_step_all.argtypes = [vp, vp, C.POINTER(PveOutputs)]
-    L.pve_scene_update.argtypes = [vp, vp, C.POINTER(PveOutputs)]
-    L.pve_compact.argtypes = [vp, vp]
-    L.pve_read_env.argtypes = [vp, C.c_int, C.POINTER(PveEnvInfo)]
-    L.pve_read_vehicles.argtypes = [vp, C.c_int, C.POINTER(PveVehicle), C.c_int, C.POINTER(C.c_int)]
-    L.pve_get_metrics.argtypes = [vp, C.POINTER(C.c_double)]
-    L.pve_state_field.argtypes = [vp, C.c_char_p, C.POINTER(vp), C.POINTER(C.c_int)]
-    L.pve_synchronize.argtypes = [vp]
-    L.pve_debug_phase_cycles.argtypes = [vp, vp]
-    L.pve_debug_stop_phase.argtypes = [vp, C.c_int]
-    L.pve_debug_last_launch.argtypes = [vp]
-    L.pve_debug_item_schedule.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int32)]
-    L.pve_debug_traffic_probe.argtypes = [vp, vp]
-    L.pve_set_actor.argtypes = [vp, vp]
-    L.pve_actor_forward.argtypes = [vp, vp, vp, vp]
-    L.pve_set_action_noise.argtypes = [vp, C.c_double, C.c_uint64, C.c_int64]
-    L.pve_set_target_networks.argtypes = [vp, vp, vp]
-    L.pve_critic_forward.argtypes = [vp, vp, vp, vp, C.c_int64]
-    L.pve_bootstrap_q.argtypes = [vp, vp, vp, vp, vp, C.c_int64]
-    L.pve_nstep_scan.argtypes = [vp, C.POINTER(PveNstep)]
-    L.pve_nstep_gather.argtypes = [vp, C.POINTER(PveNstep)]
-    L.pve_replay_reset.argtypes = [vp, C.POINTER(PveReplay)]
-    L.pve_replay_append.argtypes = [vp, C.POINTER(PveReplay), vp, vp, C.c_int64]
-    L.pve_replay_sample.argtypes = [vp, C.POINTER(PveReplay), C.c_int64, C.c_int64, vp, vp, vp, vp]
-    L.pve_learner_init.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, vp]
-    L.pve_learner_step.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, C.c_int64, C.c_int64, vp, vp]
-    L.pve_learner_step_wide.argtypes = [vp, C.POINTER(PveLearner), vp, vp, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp]
-    L.pve_prio_scratch_bytes.restype = C.c_size_t
-    L.pve_prio_scratch_bytes.argtypes = [C.c_int64]
-    L.pve_prio_reset.argtypes = [vp, C.POINTER(PvePrio)]
-    L.pve_prio_rank.argtypes = [vp, C.POINTER(PvePrio)]
-    L.pve_prio_sample.argtypes = [vp, C.POINTER(PvePrio), C.c_int64, C.c_int64, C.c_float, vp, vp, vp, vp, vp, vp]
-    L.pve_prio_update.argtypes = [vp, C.POINTER(PvePrio), vp, vp, vp, C.c_int64]
-    L.pve_generate_arrivals.argtypes = [vp, C.POINTER(PveArrivalGen), vp, vp, vp]
-    L.pve_step_all_actor.argtypes = [vp, vp, vp, vp, C.POINTER(PveOutputs)]
-    L.pve_step_many.argtypes = [vp, C.POINTER(PveRollout), C.POINTER(PveOutputs)]
-    L.pve_stats_scratch_bytes.restype = C.c_size_t
-    L.pve_stats_scratch_bytes.argtypes = [C.c_int, C.c_int]
-    L.pve_rollout_stats.argtypes = [vp, C.POINTER(PveStats)]
-    L.pve_metrics_groups.argtypes = [vp, vp, C.c_int, vp]
     # (_declare also dresses libraries that load_library has not vetted -- the tests' emulators, which may be builds of sources
     #  older than include/pve_env_debug.h: the diagnostics hook is declared where it exists, and last_variant() says so where not)
-    debug = tuple(n for n in EXPORTS_DEBUG if hasattr(L, n))
-    if debug:
-        L.pve_debug_last_variant.argtypes = [vp, C.POINTER(PveLaunchVariant)]
-    for name in EXPORTS + EXPORTS_EXT + EXPORTS_STATS + debug:
-        if name not in ("pve_last_error", "pve_workspace_bytes", "pve_default_config", "pve_prio_scratch_bytes", "pve_stats_scratch_bytes"):
-            getattr(L, name).restype = C.c_int
-    L.pve_default_config.restype = None
+    for header, group in PROTOTYPES.items():
+        for name, (restype, argtypes) in group.items():
+            if header != "pve_env_debug.h" or hasattr(L, name):
+                f = getattr(L, name)
+                f.restype, f.argtypes = restype, argtypes
     return L
 
 
@@ -217,7 +212,7 @@ def load_library(path=None):
         raise PveError("%s not found: build the HIP library first (python -c 'import __graft_entry__ as g; "
                        "g.build()' or make -C %s/csrc). There is no CPU fallback." % (p, _HERE))
     dll = C.CDLL(p)
-    missing = [n for n in EXPORTS + EXPORTS_EXT + EXPORTS_STATS + EXPORTS_DEBUG if not hasattr(dll, n)]
+    missing = [n for group in PROTOTYPES.values() for n in group if not hasattr(dll, n)]
     if missing:       # (the target-network entry points were added within ABI 9: an older build lacks the symbols)
         raise PveError("%s is an older build: it lacks %s (rebuild it)" % (p, ", ".join(missing)))
     L = _declare(dll)

@@ -745,7 +745,7 @@ class BatchedIntersections:
         k = self.lib.pve_debug_last_launch(self._h)
         if k < 0 or k > 3:                              # (a negative PVE_ERR_* must not index the tuple from its end)
             check(self.lib, k if k < 0 else -1, "pve_debug_last_launch")
-        return ("none", "tick", "resident", "persistent")[k]
+        return _capi.LAUNCH_NAMES[k]
 
     def last_variant(self):
         """Which kernel variant the last stepping call launched, as a dict (pve_debug_last_variant, include/pve_env_debug.h):
@@ -758,7 +758,7 @@ class BatchedIntersections:
             raise PveError("this library is an older build: it lacks pve_debug_last_variant (rebuild it)")
         check(self.lib, self.lib.pve_debug_last_variant(self._h, C.byref(v)), "pve_debug_last_variant")
         d = {n: int(getattr(v, n)) for n, _t in _capi.PveLaunchVariant._fields_ if n != "reserved"}
-        d["kind"] = ("none", "tick", "resident", "persistent")[d["kind"]]
+        d["kind"] = _capi.LAUNCH_NAMES[d["kind"]]
         return d
 
     # ------------------------------------------------------------------ host read-back

@@ -28,11 +28,12 @@ from .critic import KEYS, flat_critic_weights
 N_ACTOR, N_CRITIC = _capi.PVE_ACTOR_N_WEIGHTS, _capi.PVE_CRITIC_N_WEIGHTS
 N_GRADS = N_CRITIC + N_ACTOR
 # float offsets of the block's segments (include/pve_env.h PVE_LEARNER_*)
-ACTOR, CRITIC, TARGET_ACTOR, TARGET_CRITIC = 0, 6396, 13240, 19636
-M_ACTOR, V_ACTOR, M_CRITIC, V_CRITIC = 26480, 32876, 39272, 46116
-POWERS, STEPS, GRAD, N_FLOATS = 52960, 52964, 52968, 66208
+ACTOR, CRITIC, TARGET_ACTOR = _capi.LEARNER_ACTOR, _capi.LEARNER_CRITIC, _capi.LEARNER_TARGET_ACTOR
+TARGET_CRITIC, M_ACTOR, V_ACTOR = _capi.LEARNER_TARGET_CRITIC, _capi.LEARNER_M_ACTOR, _capi.LEARNER_V_ACTOR
+M_CRITIC, V_CRITIC, POWERS = _capi.LEARNER_M_CRITIC, _capi.LEARNER_V_CRITIC, _capi.LEARNER_POWERS
+STEPS, GRAD, N_FLOATS = _capi.LEARNER_STEPS, _capi.LEARNER_GRAD, _capi.LEARNER_N_FLOATS
 GRAD_ACTOR = GRAD + 6844
-CRITIC_ONLY = 0x1
+CRITIC_ONLY = _capi.LEARN_CRITIC_ONLY
 SLICE, WIDE_ROW = _capi.LEARN_SLICE, _capi.LEARNER_WIDE_ROW         # step_wide: rows per slice, workspace floats per slice
 
 

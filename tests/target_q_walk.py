@@ -10,9 +10,10 @@ import functools
 
 import numpy as np
 
+from pve_mcc_amd._capi import F_ALIVE, F_CTL, F_DELETED, F_DONE, F_LOCK     # noqa: F401  (PVE_F_* of include/pve_env.h)
+
 TQ_RING = 128                     # TQ_RING of csrc/pve_critic.h
 CHUNK, TILE, WAVES = 64, 32, 4
-F_ALIVE, F_CTL, F_DONE, F_DELETED, F_LOCK = 0x01, 0x02, 0x04, 0x08, 0x20     # PVE_F_* of include/pve_env.h
 
 BOOT_PER_CU, CRITIC_PER_CU = 2, 4                 # launch_bootstrap_q / launch_critic of csrc/pve_hip.hip
 BOOT_PASS = 256 * BOOT_PER_CU * WAVES * CHUNK     # rows one pass of the full bootstrap grid covers: 131 072

@@ -146,10 +146,10 @@ def test_distribution_of_the_keyed_draws():
 # ------------------------------------------------------------------ 4. the C ABI through the emulator library
 def test_abi_version_and_export():
     lib = emulator_lib()
-    assert _capi.ABI_VERSION == 9 and lib.pve_abi_version() == 9
+    assert lib.pve_abi_version() == _capi.ABI_VERSION          # (against the header: tests/test_binding_contract.py)
     assert "pve_set_action_noise" in _capi.EXPORTS and hasattr(lib, "pve_set_action_noise")
     header = open(os.path.join(ROOT, "include", "pve_env.h")).read()
-    assert "#define PVE_ABI_VERSION 9" in header and "main.py:44, :239" in header
+    assert "main.py:44, :239" in header
 
 
 def closed_loop(b, ticks):

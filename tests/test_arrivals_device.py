@@ -253,17 +253,16 @@ def test_generated_stream_8_lanes_with_intentions_through_the_emulator_against_t
 def test_entry_point_on_the_emulator():
     lib = emulator_lib()
     assert _capi.EXPORTS_EXT == ("pve_generate_arrivals",) and hasattr(lib, "pve_generate_arrivals")
-    assert lib.pve_abi_version() == 9 and _capi.ABI_VERSION == 9
+    assert lib.pve_abi_version() == _capi.ABI_VERSION
     header = open(os.path.join(ROOT, "include", "pve_env.h")).read()
-    for text in ("#define PVE_ABI_VERSION 9", "0x41525256", "0x54494D45", "0x494E5445", "0x4E54494F", "main.py:228-229", ":388-389",
+    for text in ("0x41525256", "0x54494D45", "0x494E5445", "0x4E54494F", "main.py:228-229", ":388-389",
                  "ref :381, :390", "} pve_arrival_gen;", "include/pve_env_arrivals.h"):
         assert text in header, text
-    # the extension header declares exactly the entry points of EXPORTS_EXT, and the product library exports them
+    # the extension header's prototype, and the product library exports it (that the header declares exactly EXPORTS_EXT, the
+    # version, the signature's classes and the struct's layout: tests/test_binding_contract.py)
     ext = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pve_env_arrivals.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(pve_[a-z_]+)\s*\(", ext))) == sorted(_capi.EXPORTS_EXT)
     assert "int pve_generate_arrivals(pve_handle h, const pve_arrival_gen *g, double *arrivals" in ext
     assert all(hasattr(_capi.load_library(), n) for n in _capi.EXPORTS_EXT) and not set(_capi.EXPORTS) & set(_capi.EXPORTS_EXT)
-    assert C.sizeof(_capi.PveArrivalGen) == 56
     b12 = make_batch(np.full((4, 12), np.inf), 3, 64, "emu", outputs=("obs_post", "flags"))
     b8 = make_batch(np.full((4, 8), np.inf), 3, 64, "emu", outputs=("obs_post", "flags"), lane_num=8)
     keep = []

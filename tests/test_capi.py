@@ -1,6 +1,6 @@
-"""C-ABI library checks that need no GPU: libpveenv.so loads, exports every symbol that
-include/pve_env.h declares, and fails loudly (no CPU fallback) without a device; argument
-validation and call-sequence errors (exercised through the emulator build of the same C-ABI source)."""
+"""C-ABI library checks that need no GPU: libpveenv.so loads and fails loudly (no CPU fallback) without a device; argument
+validation and call-sequence errors (exercised through the emulator build of the same C-ABI source).  That the binding and the
+libraries agree with include/*.h -- symbols, signatures, layouts, constants -- is tests/test_binding_contract.py."""
 import ctypes as C
 import os
 import re
@@ -17,31 +17,16 @@ from tests.hip_adapter import emulator_lib
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 
-def header_symbols():
-    src = open(os.path.join(ROOT, "include", "pve_env.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(pve_[a-z_]+)\s*\(", src)))
-
-
 def test_library_exports_every_declared_symbol():
+    """(every symbol of every header, by the table: tests/test_binding_contract.py)"""
     import __graft_entry__
     __graft_entry__.build()
     lib = _capi.load_library()
-    syms = header_symbols()
-    assert len(syms) >= 17
-    for s in syms:
+    for s in _capi.EXPORTS:
         assert hasattr(lib, s), "libpveenv.so does not export %s" % s
-    assert sorted(_capi.EXPORTS) == syms, "binding and header disagree"
     assert lib.pve_abi_version() == _capi.ABI_VERSION
     assert lib.pve_workspace_bytes(4096, 128) > 4096 * 128 * 84
     assert lib.pve_workspace_bytes(10, 100) == 0
-
-
-def test_struct_sizes_match_header():
-    assert C.sizeof(_capi.PveConfig) == 9 * 8 + 8
-    assert C.sizeof(_capi.PveOutputs) == 10 * 8
-    assert C.sizeof(_capi.PveVehicle) == 7 * 8 + 17 * 4 + 4   # padded to 8
-    assert C.sizeof(_capi.PveEnvInfo) == 8 + 4 * (1 + 12 + 12 + 3 + 3 * 16 + 1 + 1)
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
@@ -163,15 +148,15 @@ def test_item_schedule_of_the_persistent_call_has_no_tiny_items():
 
 
 def test_debug_extension_header_and_launch_record():
-    """include/pve_env_debug.h: the record's layout against the binding, exactly EXPORTS_DEBUG declared, disjoint from the other
-    tuples (which keep their counts), exported by the product library and by the emulator"""
+    """include/pve_env_debug.h: the record's field names against the binding, EXPORTS_DEBUG disjoint from the other tuples and
+    absent from the main header, exported by the product library and by the emulator (layout, signature and the header's own
+    list of entry points: tests/test_binding_contract.py)"""
     ext = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pve_env_debug.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(pve_[a-z_]+)\s*\(", ext))) == sorted(_capi.EXPORTS_DEBUG) == ["pve_debug_last_variant"]
+    assert _capi.EXPORTS_DEBUG == ("pve_debug_last_variant",)
     body = re.search(r"typedef struct pve_launch_variant \{(.*?)\} pve_launch_variant;", ext, flags=re.S).group(1)
     fields = re.findall(r"int32_t\s+([a-z_]+)(?:\[(\d+)\])?;", body)
     assert [n for n, _ in fields] == [n for n, _ in _capi.PveLaunchVariant._fields_]
-    assert C.sizeof(_capi.PveLaunchVariant) == 4 * sum(int(k or 1) for _, k in fields) == 16 * 4
-    assert len(_capi.EXPORTS) == 44 and _capi.EXPORTS_EXT == ("pve_generate_arrivals",)
+    assert _capi.EXPORTS_EXT == ("pve_generate_arrivals",)
     assert not set(_capi.EXPORTS_DEBUG) & set(_capi.EXPORTS + _capi.EXPORTS_EXT + _capi.EXPORTS_STATS)
     main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pve_env.h")).read(), flags=re.S)
     assert not any(n in main for n in _capi.EXPORTS_DEBUG)

@@ -118,8 +118,8 @@ def test_critic_canonical_vs_graph():
 def test_exports_header_and_binding_agree():
     lib = emulator_lib()
     header = open(os.path.join(ROOT, "include", "pve_env.h")).read()
-    assert _capi.ABI_VERSION == 9 and lib.pve_abi_version() == 9 and "#define PVE_ABI_VERSION 9" in header
-    assert "#define PVE_CRITIC_N_WEIGHTS 6841" in header and "main.py:253-260" in header and "PVE_ABI_VERSION stays 9" in header
+    assert lib.pve_abi_version() == _capi.ABI_VERSION          # (version and constants against the header: tests/test_binding_contract.py)
+    assert "main.py:253-260" in header and "PVE_ABI_VERSION stays 9" in header
     for name in ("pve_set_target_networks", "pve_critic_forward", "pve_bootstrap_q"):
         assert name in _capi.EXPORTS and hasattr(lib, name) and ("int %s(pve_handle h" % name) in header
     assert lib.pve_critic_forward.argtypes[-1] is C.c_int64 and lib.pve_bootstrap_q.argtypes[-1] is C.c_int64

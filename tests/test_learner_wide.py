@@ -8,7 +8,6 @@
   5. the C ABI's argument checks, through the CPU emulators, which have no learner kernels and say so.
 The kernels against this host build: tests/test_gpu_learner_wide.py."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -26,9 +25,8 @@ def test_layout_is_the_headers():
     assert out.tolist()[:7] == [LN.SLICE, LN.WIDE_ROW, W.ROW_CRITIC, W.ROW_ACTOR, W.ROW_LOSS, 64, 32]
     W.shim("liblearner_wide_host_sub.so").learner_wide_host_layout(S._ptr(out))
     assert out.tolist()[5:7] == [7, 5]
-    header = open(os.path.join(S.ROOT, "include", "pve_env.h")).read()
-    assert "#define PVE_LEARN_SLICE %d\n" % LN.SLICE in header and "#define PVE_LEARNER_WIDE_ROW %d\n" % LN.WIDE_ROW in header
-    assert "#define PVE_ABI_VERSION 9" in header and _capi.ABI_VERSION == 9
+    # (_capi's LEARN_SLICE and LEARNER_WIDE_ROW against the header's macros: tests/test_binding_contract.py)
+    assert (LN.SLICE, LN.WIDE_ROW) == (_capi.LEARN_SLICE, _capi.LEARNER_WIDE_ROW)
     assert LN.WIDE_ROW % 4 == 0 and LN.WIDE_ROW == 6844 + 6396 + 4
     assert [LN.wide_floats(b) for b in (1, 128, 129, 256, 257)] == [LN.WIDE_ROW * k for k in (1, 1, 2, 2, 3)]
 
@@ -176,7 +174,7 @@ def test_wide_host_build_follows_the_model(batch, n_steps, seed):
 def test_entry_point_on_the_emulator():
     from pve_mcc_amd.arrivals import synthetic_arrivals
     lib = emulator_lib()
-    assert "pve_learner_step_wide" in _capi.EXPORTS and hasattr(lib, "pve_learner_step_wide") and lib.pve_abi_version() == 9
+    assert "pve_learner_step_wide" in _capi.EXPORTS and hasattr(lib, "pve_learner_step_wide") and lib.pve_abi_version() == _capi.ABI_VERSION
     b = make_batch(synthetic_arrivals(2, rate=500.0, horizon_s=20.0, seed=1), 2, 64, "emu", outputs=("obs_post", "flags"))
     keep = []
 

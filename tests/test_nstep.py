@@ -264,7 +264,7 @@ def test_entry_points_on_the_emulator():
     lib = emulator_lib()
     for name in ("pve_nstep_scan", "pve_nstep_gather"):
         assert name in _capi.EXPORTS and hasattr(lib, name)
-    assert lib.pve_abi_version() == 9
+    assert lib.pve_abi_version() == _capi.ABI_VERSION
     for cls in (BatchedIntersections, PipelinedIntersections):
         assert callable(getattr(cls, "nstep_transitions"))
     b = make_batch(synthetic_arrivals(2, rate=500.0, horizon_s=20.0, seed=1), 2, 64, "emu", outputs=("obs_post", "reward", "flags", "env_out"))

@@ -273,13 +273,12 @@ def test_entry_points_on_the_emulator():
     names = ("pve_prio_scratch_bytes", "pve_prio_reset", "pve_prio_rank", "pve_prio_sample", "pve_prio_update")
     for name in names:
         assert name in _capi.EXPORTS and hasattr(lib, name)
-    assert lib.pve_abi_version() == 9 and _capi.ABI_VERSION == 9 and len(_capi.EXPORTS) == 44
+    assert lib.pve_abi_version() == _capi.ABI_VERSION          # (version, constants, layout against the header: tests/test_binding_contract.py)
     header = open(os.path.join(ROOT, "include", "pve_env.h")).read()
-    for text in ("#define PVE_PRIO_STATE_WORDS 4", "#define PVE_ABI_VERSION 9", "0x5052494F", "0x52414E4B", "rank_based.py:148-188",
+    for text in ("0x5052494F", "0x52414E4B", "rank_based.py:148-188",
                  "main.py:76-79", "binary_heap.py:194-221", "rank_based.py:40-80", "replay_buffer.py:13-18"):
         assert text in header, text
     assert (replay.PRIO_TAG0, replay.PRIO_TAG1) == (0x5052494F, 0x52414E4B)
-    assert C.sizeof(_capi.PvePrio) == 40 + 10 * 8
     assert lib.pve_prio_scratch_bytes(0) == 0 and lib.pve_prio_scratch_bytes(1 << 31) == 0 and lib.pve_prio_scratch_bytes(-3) == 0
     assert lib.pve_prio_scratch_bytes(500000) == 16 * 500000 + 1024 * (245 + 4) and lib.pve_prio_scratch_bytes(321) == 16 * 324 + 1024 * 5
     b = make_batch(synthetic_arrivals(2, rate=500.0, horizon_s=20.0, seed=1), 2, 64, "emu", outputs=("obs_post", "flags"))

@@ -238,11 +238,10 @@ def test_entry_points_on_the_emulator():
     lib = emulator_lib()
     for name in ("pve_replay_reset", "pve_replay_append", "pve_replay_sample"):
         assert name in _capi.EXPORTS and hasattr(lib, name)
-    assert lib.pve_abi_version() == 9 and _capi.ABI_VERSION == 9
+    assert lib.pve_abi_version() == _capi.ABI_VERSION          # (version, constants, layout against the header: tests/test_binding_contract.py)
     header = open(os.path.join(ROOT, "include", "pve_env.h")).read()
-    assert "#define PVE_REPLAY_STATE_WORDS 4" in header and "replay_buffer.py:45-53" in header and "replay_buffer.py:20-23" in header
+    assert "replay_buffer.py:45-53" in header and "replay_buffer.py:20-23" in header
     assert "0x5245504C" in header and "0x41594D45" in header and (replay.TAG0, replay.TAG1) == (0x5245504C, 0x41594D45)
-    assert C.sizeof(_capi.PveReplay) == 40
     b = make_batch(synthetic_arrivals(2, rate=500.0, horizon_s=20.0, seed=1), 2, 64, "emu", outputs=("obs_post", "flags"))
     keep = []
 

@@ -310,17 +310,16 @@ def test_metrics_groups_model_partitions_and_one_group_is_metrics():
 def test_entry_points_on_the_emulator():
     lib = emulator_lib()
     assert _capi.EXPORTS_STATS == ("pve_stats_scratch_bytes", "pve_rollout_stats", "pve_metrics_groups")
-    assert _capi.EXPORTS_EXT == ("pve_generate_arrivals",) and len(_capi.EXPORTS) == 44
-    assert lib.pve_abi_version() == 9 and _capi.ABI_VERSION == 9
+    # (that the header declares exactly EXPORTS_STATS, the version, PVE_STAT_* and pve_stats' layout: tests/test_binding_contract.py)
+    assert _capi.EXPORTS_EXT == ("pve_generate_arrivals",)
+    assert lib.pve_abi_version() == _capi.ABI_VERSION
     ext = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pve_env_stats.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(pve_[a-z_]+)\s*\(", ext))) == sorted(_capi.EXPORTS_STATS)
-    assert "int pve_rollout_stats(pve_handle h, const pve_stats *st);" in ext and "#define PVE_STAT_N 14" in ext
+    assert "int pve_rollout_stats(pve_handle h, const pve_stats *st);" in ext
     main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "pve_env.h")).read(), flags=re.S)
     assert not any(n in main for n in _capi.EXPORTS_STATS)
     product = _capi.load_library()
     assert all(hasattr(product, n) and hasattr(lib, n) for n in _capi.EXPORTS_STATS)
     assert not set(_capi.EXPORTS_STATS) & set(_capi.EXPORTS + _capi.EXPORTS_EXT)
-    assert C.sizeof(_capi.PveStats) == 80
     assert lib.pve_stats_scratch_bytes(4096, 20) == 4096 * 20 * 14 * 8 and lib.pve_stats_scratch_bytes(0, 5) == 0
     assert product.pve_stats_scratch_bytes(17, 3) == 17 * 3 * 14 * 8 and lib.pve_stats_scratch_bytes(5, -1) == 0
     b = make_batch(np.full((4, 12), np.inf), 3, 64, "emu", outputs=("obs_post", "obs_pre", "reward", "flags", "env_out"))
