@@ -430,6 +430,10 @@ int pve_replay_sample(pve_handle h, const pve_replay *rp, int64_t batch, int64_t
  * rows + pve_prio_update (below); the summaries are NOT reproduced.  The reference assigns
  * self.critic_lr after the optimizer is built, which changes nothing there; here both learning rates are read on every call.
  * block_threads: 0 = 1024; else a multiple of 64 up to 1024 (same results).
+ * epsilon: any finite float32.  A subnormal value (1e-40f) is honoured as it stands: sqrtf(v) + epsilon is a float32 add with
+ * subnormal operands and results kept, as every operation of the step is.  epsilon = 0 is accepted as well; a parameter whose
+ * gradient has been exactly zero in every step (m = v = 0: a weight behind a unit that never fires) then takes 0 / 0, and it and
+ * its target become NaN.
  * Errors (PVE_ERR_INVALID): null pointers, batch < 1, n_batches < 1, batch * n_batches > 2^31 - 1, params / rows / networks not
  * 16-byte aligned (the others: 4), learning rates, epsilon or tau not finite, tau outside [0, 1], beta outside [0, 1), a bad
  * block_threads, a backend without the kernel.  Both calls are asynchronous on the handle's stream and need no pve_reset. */

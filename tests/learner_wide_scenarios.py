@@ -106,6 +106,20 @@ def host_run(bsz, n, warmed, zero_units, critic_only=False):
     return inp, P, losses, grads
 
 
+@functools.lru_cache(maxsize=None)
+def range_run(name, bsz, lib=None):
+    """the wide host build (lib: another library name) on a case of learner_scenarios.RANGE_CASES at a batch of bsz rows: the
+    case's networks, start block, hyper-parameters and number of minibatches, the minibatches drawn as minibatches() above draws
+    them -> (inputs, block after, losses, grads); computed once, read-only"""
+    c = S.range_case(name)
+    P = S.range_start(name).copy()
+    inp = S.range_inputs(name, bsz, wide=True)
+    losses, grads = host_step_wide(P, *inp, lib=shim(lib) if lib else None, **c["hyper"])
+    for a in inp + (P, losses, grads):
+        a.setflags(write=False)
+    return inp, P, losses, grads
+
+
 def wide_batches():
     """(batch, n_steps, seed): what the wide header is held to the semantics on, and its bar is measured on"""
     return ((129, 5, 11), (300, 5, 12), (1024, 5, 13))

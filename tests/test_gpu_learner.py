@@ -1,7 +1,9 @@
 """The learner step on the GPU (pve_learner_init / pve_learner_step, k_learner_step) against a g++ build of the same header
 (tests/learner_host, held to LearnerModel and to autograd in tests/test_learner.py): the whole parameter block, the losses and
-the gradients, bit for bit.  Then its use: install() against weights copied through the host, and one pass of roll-out ->
-n-step transitions -> replay memory -> sample -> step."""
+the gradients, bit for bit -- on the fixture's magnitudes and across the float32 range (subnormal gradients, moments and beta
+powers, overflow, hyper-parameters at the ends of their ranges: tests/learner_scenarios.py, families A .. F).  Then its use:
+install() against weights copied through the host, and one pass of roll-out -> n-step transitions -> replay memory -> sample ->
+step."""
 import functools
 
 import numpy as np
@@ -56,14 +58,22 @@ def host_run(bsz, n, warmed, zero_units, critic_only=False):
     return inp, P, losses, grads
 
 
-def check_block(lrn, P, what):
-    got = _np(lrn.params)
-    if not np.array_equal(S.bits32(got), S.bits32(P)):
-        names = ("actor", "critic", "target_actor", "target_critic", "m_actor", "v_actor", "m_critic", "v_critic", "powers", "steps", "grad")
-        offs = (LN.ACTOR, LN.CRITIC, LN.TARGET_ACTOR, LN.TARGET_CRITIC, LN.M_ACTOR, LN.V_ACTOR, LN.M_CRITIC, LN.V_CRITIC, LN.POWERS, LN.STEPS,
-                LN.GRAD, LN.N_FLOATS)
-        bad = {n: int((S.bits32(got[a:z]) != S.bits32(P[a:z])).sum()) for n, a, z in zip(names, offs[:-1], offs[1:])}
-        raise AssertionError("%s: the block differs from the host build's: words per segment %s" % (what, bad))
+def check_block(lrn, P, what, nan_ok=False):
+    """the device block against the host build's, bit for bit, no NaN in either; nan_ok (family D of the range only): equal NaN
+    masks, every other word bit-equal (learner_scenarios.same_words).  Differences are reported per segment."""
+    S.check_words(_np(lrn.params), P, what + ": the block", nan_ok=nan_ok)
+
+
+def range_learner(b, name, threads):
+    """a Learner at the start of a case of learner_scenarios.RANGE_CASES, with the case's hyper-parameters: a fresh state comes
+    from pve_learner_init (and is compared), any other is loaded"""
+    c = S.range_case(name)
+    lrn = Learner(b, *S.range_networks(name), block_threads=threads, **c["hyper"])
+    if c["warmed"] or c["long"]:
+        lrn.load_state_dict({"params": torch.from_numpy(S.range_start(name).copy())})
+    else:
+        check_block(lrn, S.range_start(name), name + " (init)")
+    return lrn
 
 
 # ------------------------------------------------------------------ 1. the kernel == the host build, bit for bit
@@ -146,6 +156,67 @@ def test_gpu_state_dict_round_trip():
     for l in (lrn, twin):
         l.step(*(dev(x[2:], b) for x in inp))
         check_block(l, P, "state_dict")
+
+
+# ------------------------------------------------------------------ 1b. the same across the float32 range (learner_scenarios: A .. F)
+@pytest.mark.parametrize("name", list(S.RANGE_CASES))
+def test_gpu_range_equals_the_host_build(name):
+    """Subnormal gradients and moments (A), the state of a long run with a subnormal b1p (C), overflow (D), hyper-parameters at the
+    ends of their ranges (E), squares that underflow in the input LayerNorm (F): block, losses and gradients bit for bit at 256
+    and 1024 threads.  tests/test_learner.py asserts that the host results are in the regime.  D alone may hold NaN: there the
+    NaN masks are equal and every other word, infinities included, is bit-equal."""
+    b = batch()
+    c = S.range_case(name)
+    inp, P, losses, grads = S.range_run(name)
+    rows, act7, target = (dev(x, b) for x in inp)
+    for threads in (256, 1024):
+        what = "%s, %d threads" % (name, threads)
+        lrn = range_learner(b, name, threads)
+        got_l, got_g = lrn.step(rows, act7, target, losses=True, grads=True)
+        S.check_words(_np(got_l), losses, what + ": losses", nan_ok=c["nan_ok"])
+        S.check_words(_np(got_g), grads, what + ": grads", nan_ok=c["nan_ok"])
+        check_block(lrn, P, what, nan_ok=c["nan_ok"])
+        assert lrn.steps() == int(P[LN.STEPS:LN.STEPS + 1].view(np.int32)[0])
+        print("%s: equal to the host build (%d subnormal words, %d NaN, %d infinities in block and gradients)"
+              % (what, S.count_subnormal(P[:LN.STEPS]) + S.count_subnormal(grads), S.count_nan(P) + S.count_nan(grads),
+                 int(np.isinf(P).sum() + np.isinf(grads).sum())))
+
+
+def test_gpu_long_run_equals_the_host_build():
+    """Family C: 1 100 steps of batch 2 in 22 calls of 50 minibatches.  The block after call 17 (step 850: b1p subnormal and still
+    moving) and after call 22 (step 1 100: b1p at its fixed point of 4 quanta) equals the host build's; then the policy of that
+    state is installed: act() equals the act() of the same weights copied through the host."""
+    b = batch()
+    rows, act7, target = (dev(x, b) for x in S.long_run_inputs())
+    host = S.long_run()
+    lrn = device_learner(b)
+    for call in range(S.LONG_STEPS // S.LONG_CALL):
+        a = call * S.LONG_CALL
+        lrn.step(rows[a:a + S.LONG_CALL], act7[a:a + S.LONG_CALL], target[a:a + S.LONG_CALL])
+        if a + S.LONG_CALL in (S.LONG_MOVING, S.LONG_STEPS):
+            check_block(lrn, host[a + S.LONG_CALL], "long run, step %d" % (a + S.LONG_CALL))
+            print("long run, step %d: equal to the host build, b1p %.6e" % (a + S.LONG_CALL, host[a + S.LONG_CALL][LN.POWERS]))
+    assert lrn.steps() == S.LONG_STEPS and _np(lrn.params)[LN.POWERS] == S.B1P_FIXED_POINT
+    state = {"params": torch.from_numpy(_np(lrn.params).copy())}
+    g = load_critic_golden()
+    arr = synthetic_arrivals(3, rate=1300.0, horizon_s=45.0, seed=11)
+    acts = []
+    for through_host in (False, True):
+        e = make_batch(arr, 3, 64, "hip", outputs=TRAIN_OUTS)
+        e.reset()
+        e.set_actor(flat_weights(load_weights()))
+        e.set_target_networks(actor=g.weights["target_actor"], critic=g.weights["target_critic"])
+        e.step_many(150, source="actor", trajectory=True)
+        there = device_learner(e)
+        there.load_state_dict(state)
+        if through_host:
+            e.set_actor(_np(there.actor_weights).copy())
+        else:
+            there.install()
+        acts.append(e.act().clone())
+        e.synchronize()
+    assert same_bits(acts[0], acts[1]) and bool((acts[0] != 0).any()) and bool(torch.isfinite(acts[0]).all())
+    assert not np.array_equal(_np(lrn.actor_weights), S.fixture().actor)
 
 
 # ------------------------------------------------------------------ 2. install(): the block's segments feed set_actor / set_target_networks

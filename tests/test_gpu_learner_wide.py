@@ -44,14 +44,10 @@ def device_learner(b, zero_units=False, warmed=False, threads=0):
     return lrn
 
 
-def check_block(lrn, P, what):
-    got = _np(lrn.params)
-    if not np.array_equal(S.bits32(got), S.bits32(P)):
-        names = ("actor", "critic", "target_actor", "target_critic", "m_actor", "v_actor", "m_critic", "v_critic", "powers", "steps", "grad")
-        offs = (LN.ACTOR, LN.CRITIC, LN.TARGET_ACTOR, LN.TARGET_CRITIC, LN.M_ACTOR, LN.V_ACTOR, LN.M_CRITIC, LN.V_CRITIC, LN.POWERS, LN.STEPS,
-                LN.GRAD, LN.N_FLOATS)
-        bad = {n: int((S.bits32(got[a:z]) != S.bits32(P[a:z])).sum()) for n, a, z in zip(names, offs[:-1], offs[1:])}
-        raise AssertionError("%s: the block differs from the host build's: words per segment %s" % (what, bad))
+def check_block(lrn, P, what, nan_ok=False):
+    """the device block against the host build's, bit for bit, no NaN in either; nan_ok (family D of the range only): equal NaN
+    masks, every other word bit-equal (learner_scenarios.same_words).  Differences are reported per segment."""
+    S.check_words(_np(lrn.params), P, what + ": the block", nan_ok=nan_ok)
 
 
 # ------------------------------------------------------------------ 1. the kernels == the host build, bit for bit
@@ -76,6 +72,30 @@ def test_gpu_wide_step_equals_the_host_build(bsz, n, threads, warmed, zero_units
     assert np.array_equal(S.bits32(_np(got_g)), S.bits32(grads)), what
     check_block(lrn, P, what)
     assert lrn.steps() == n + (5 if warmed else 0) and np.all(np.isfinite(P)) and np.all(np.isfinite(grads))
+
+
+# ------------------------------------------------------------------ 1b. the same across the float32 range (learner_scenarios: A .. F)
+@pytest.mark.parametrize("name", list(S.RANGE_CASES))
+def test_gpu_wide_range_equals_the_host_build(name):
+    """The cases of tests/test_gpu_learner.py through the slice and apply kernels: 130 rows (two slices, the second of 2 rows) and
+    300 rows (three, the last of 44), two grids each (one workgroup per slice; one or two workgroups walking the slices), 256 and
+    1024 threads.  Family C here: three minibatches from the long run's state at step 850 (b1p subnormal, moving) and at step
+    1 100 (its fixed point).  D alone may hold NaN: equal NaN masks, every other word bit-equal."""
+    b = batch()
+    c = S.range_case(name)
+    for bsz, threads, groups in ((130, 256, 0), (130, 1024, 1), (300, 1024, 0), (300, 256, 2)):
+        inp, P, losses, grads = W.range_run(name, bsz)
+        what = "%s, batch %d, %d threads, groups %d" % (name, bsz, threads, groups)
+        lrn = Learner(b, *S.range_networks(name), block_threads=threads, **c["hyper"])
+        lrn.load_state_dict({"params": torch.from_numpy(S.range_start(name).copy())})
+        got_l, got_g = lrn.step_wide(*(dev(x, b) for x in inp), losses=True, grads=True, groups=groups)
+        S.check_words(_np(got_l), losses, what + ": losses", nan_ok=c["nan_ok"])
+        S.check_words(_np(got_g), grads, what + ": grads", nan_ok=c["nan_ok"])
+        check_block(lrn, P, what, nan_ok=c["nan_ok"])
+        assert lrn.steps() == int(P[LN.STEPS:LN.STEPS + 1].view(np.int32)[0])
+        print("%s: equal to the host build (%d subnormal words, %d NaN, %d infinities in block and gradients)"
+              % (what, S.count_subnormal(P[:LN.STEPS]) + S.count_subnormal(grads), S.count_nan(P) + S.count_nan(grads),
+                 int(np.isinf(P).sum() + np.isinf(grads).sum())))
 
 
 # ------------------------------------------------------------------ 2. up to one slice: the existing kernel's bits

@@ -225,6 +225,203 @@ def test_critic_only_leaves_the_actor_alone(warmed):
     assert np.array_equal(S.bits32(l2[0, 0]), S.bits32(losses[0, 0])) and np.array_equal(S.bits32(g2[0, :LN.N_CRITIC]), S.bits32(grads[0, :LN.N_CRITIC]))
 
 
+# ------------------------------------------------------------------ 4b. the float32 range (learner_scenarios: families A .. F)
+# First that every scenario IS in the regime it is named for (on the host build; a scenario that never leaves the normal range
+# proves nothing), then what can be said there without a GPU.  tests/test_gpu_learner.py holds the kernel to these host results.
+SUB = "liblearner_host_sub.so"
+
+
+def _subnormal_words(P, grads):
+    seg = S.segments(P)
+    return dict(grads=S.count_subnormal(grads), **{k: S.count_subnormal(seg[k]) for k in ("m_actor", "v_actor", "m_critic", "v_critic")})
+
+
+@pytest.mark.parametrize("name", [n for n in S.RANGE_CASES if n[0] == "A"])
+def test_family_a_is_subnormal(name):
+    """scaled heads: thousands of subnormal words in the gradients and in Adam's moments, everything finite; from a fresh state and
+    from one with non-zero moments alike"""
+    s = S.range_case(name)["s"]
+    _, P, losses, grads = S.range_run(name)
+    n = _subnormal_words(P, grads)
+    print("%s: subnormal words %s of %d non-zero gradient words" % (name, n, int((grads != 0).sum())))
+    assert np.all(np.isfinite(P)) and np.all(np.isfinite(grads)) and np.all(np.isfinite(losses))
+    if s in (62, 70):
+        assert n["grads"] >= 1000
+    if s == 62:
+        assert n["v_critic"] >= 1000
+    if s == 100:
+        assert n["m_critic"] >= 1000 and n["v_actor"] >= 100
+    if S.range_case(name)["warmed"]:
+        start = S.segments(S.range_start(name))
+        # (non-zero moments, powers below beta; at s = 100 every g * g underflows to zero during the warm-up, and v with it)
+        assert all(np.any(start[k] != 0) for k in ("m_actor", "m_critic")) and start["powers"][0] < S.HYPER["beta1"]
+        assert all(np.any(start[k] != 0) == (s < 100) for k in ("v_actor", "v_critic"))
+        assert np.array_equal(S.bits32(start["critic"][:LN.N_CRITIC]), S.bits32(S.range_networks(name)[1]))    # (the scaled head is still there)
+
+
+def test_family_c_reaches_the_fixed_point_of_b1p():
+    """1 100 steps of batch 2: b1p *= 0.9f is subnormal and moving at step 850 and sits at 4 quanta at step 1 100, where
+    0.9f * 4 quanta rounds back to 4; calls of 50 minibatches == one call of 1 100 == the sub-block build"""
+    L = S.long_run()
+    P = L[S.LONG_STEPS]
+    for k in (S.LONG_MOVING, S.LONG_MOVING + S.LONG_CALL, S.LONG_STEPS):
+        print("step %4d: b1p %.6e (%d quanta), b2p %.6f" % (k, L[k][LN.POWERS], S.bits32(L[k][LN.POWERS:LN.POWERS + 1])[0], L[k][LN.POWERS + 1]))
+    assert S.bits32(P[LN.POWERS:LN.POWERS + 1])[0] == S.bits32(S.B1P_FIXED_POINT) == 4 and P[LN.POWERS + 2] == S.B1P_FIXED_POINT
+    assert np.float32(S.HYPER["beta1"]) * S.B1P_FIXED_POINT == S.B1P_FIXED_POINT
+    assert int(P[LN.STEPS:LN.STEPS + 1].view(np.int32)[0]) == S.LONG_STEPS and all(np.all(np.isfinite(b)) for b in L.values())
+    moving, later = L[S.LONG_MOVING][LN.POWERS], L[S.LONG_MOVING + S.LONG_CALL][LN.POWERS]
+    assert S.B1P_FIXED_POINT < later < moving < S.TINY
+    one, sub = S.long_run(call=S.LONG_STEPS), S.long_run(lib=SUB)
+    assert np.array_equal(S.bits32(one[S.LONG_STEPS]), S.bits32(P))
+    for k in (S.LONG_MOVING, S.LONG_STEPS):
+        assert np.array_equal(S.bits32(sub[k]), S.bits32(L[k])), k
+
+
+@pytest.mark.parametrize("name", [n for n in S.RANGE_CASES if n[0] in "CEF"])
+def test_range_cases_stay_finite_and_keep_their_bits_across_builds(name):
+    """C (three minibatches of 65 rows from the long run's state), E and F: the block stays finite; the sub-block build and three
+    single calls give the same bits"""
+    c = S.range_case(name)
+    inp, P, losses, grads = S.range_run(name)
+    assert np.all(np.isfinite(P)) and np.all(np.isfinite(grads)) and np.all(np.isfinite(losses)), name
+    _, P2, l2, g2 = S.range_run(name, lib=SUB)
+    assert np.array_equal(S.bits32(P), S.bits32(P2)) and np.array_equal(S.bits32(losses), S.bits32(l2)) and np.array_equal(S.bits32(grads), S.bits32(g2))
+    Q = S.range_start(name).copy()
+    for k in range(c["n"]):
+        l1, g1 = S.host_step(Q, *(x[k] for x in inp), **c["hyper"])
+        assert np.array_equal(S.bits32(l1[0]), S.bits32(losses[k])) and np.array_equal(S.bits32(g1[0]), S.bits32(grads[k]))
+    assert np.array_equal(S.bits32(Q), S.bits32(P))
+    if c["long"]:
+        assert 0 < S.range_start(name)[LN.POWERS] < S.TINY and 0 < P[LN.POWERS] < S.TINY
+
+
+def test_family_e_hyper_parameters_do_what_they_say():
+    """each end of a range is visible in the block, so the bit-equality of tests/test_gpu_learner.py says that the kernel received it"""
+    seg = {n: (S.segments(S.range_start(n)), S.segments(S.range_run(n)[1])) for n in S.RANGE_CASES if n[0] == "E"}
+    for net in ("actor", "critic"):
+        a, z = seg["E-tau-1"]
+        assert np.array_equal(S.bits32(z["target_" + net]), S.bits32(a["target_" + net])) and not np.array_equal(z[net], a[net])
+        a, z = seg["E-tau-0"]
+        assert np.array_equal(S.bits32(z["target_" + net]), S.bits32(z[net])) and not np.array_equal(z[net], a[net])
+    a, z = seg["E-beta1-0"]
+    assert a["powers"][0] > 0 and z["powers"][0] == 0 and z["powers"][2] == 0 and z["powers"][1] > 0
+    a, z = seg["E-lr-0-1"]
+    assert np.array_equal(S.bits32(z["actor"]), S.bits32(a["actor"])) and np.any(z["m_actor"] != a["m_actor"])
+    assert np.abs(z["critic"] - a["critic"]).max() > 0.5                                   # (critic_lr = 1: Adam's steps are of order 1)
+    # epsilon = 1e-40 is a float32 subnormal and is honoured: the zero-gradient weights of the exact-zero-ReLU networks divide
+    # 0 by sqrt(v) + 1e-40 and stay; with epsilon = 0 they divide 0 by 0 (include/pve_env.h says so)
+    assert 0 < np.float32(1e-40) < S.TINY
+    name = "E-epsilon-1e-40"
+    a, z = seg[name]
+    dead = (z["v_critic"] == 0) & (z["m_critic"] == 0)
+    assert dead.sum() >= 64 and np.array_equal(S.bits32(z["critic"][dead]), S.bits32(a["critic"][dead]))
+    Q = S.range_start(name).copy()
+    S.host_step(Q, *S.range_inputs(name), want=False, **dict(S.range_case(name)["hyper"], epsilon=0.0))
+    print("epsilon = 0 on the exact-zero-ReLU networks: %d NaN words in the block" % S.count_nan(Q))
+    assert S.count_nan(Q) > 0 and S.count_nan(S.range_run(name)[1]) == 0
+
+
+def test_family_f_underflows_inside_the_input_layernorm():
+    """the observable: `r0`, the rstd of the input LayerNorm that LearnerModel's tape exposes (learner_scenarios.underflowed_input_rows)"""
+    rows = S.range_inputs("F-tiny-rows")[0]
+    n = S.underflowed_input_rows(rows)
+    print("F-tiny-rows: %d of %d rows have d * d underflowed to zero in the input LayerNorm" % (n, rows.shape[0] * rows.shape[1]))
+    assert n >= 1 and S.underflowed_input_rows(S.minibatches(65, 2, seed=9)[0]) == 0
+
+
+def test_same_words():
+    """the comparison tests/test_gpu_learner.py uses where NaN occurs: equal NaN masks, every other word bit-equal"""
+    w = lambda *bits: np.array(bits, np.uint32).view(np.float32)                         # noqa: E731
+    qnan, xnan, snan, inf, ninf = 0x7FC00000, 0xFFC00000, 0x7F800001, 0x7F800000, 0xFF800000
+    assert S.is_nan_word(np.array([qnan, xnan, snan, inf, ninf, 0, 1], np.uint32)).tolist() == [True, True, True, False, False, False, False]
+    assert S.same_words(w(qnan, inf, 1, 0), w(xnan, inf, 1, 0)) and S.same_words(w(snan), w(qnan))
+    assert not S.same_words(w(qnan, inf), w(qnan, ninf))                                 # an infinity keeps its sign
+    assert not S.same_words(w(qnan, 5), w(5, qnan)) and not S.same_words(w(qnan), w(inf)) and not S.same_words(w(0), w(0x80000000))
+    assert not S.same_words(w(1), w(2)) and not S.same_words(w(1, 2), w(1)) and S.same_words(w(4), w(4))
+    S.check_words(w(qnan, 7), w(xnan, 7), "nan_ok", nan_ok=True)
+    for got, ref, ok in ((w(qnan, 7), w(xnan, 7), False), (w(qnan, 7), w(qnan, 8), True), (w(3, 7), w(3, 8), False)):
+        with pytest.raises(AssertionError):
+            S.check_words(got, ref, "differs", nan_ok=ok)
+
+
+def test_family_d_overflows_and_keeps_its_words_across_builds():
+    """targets x 2^60: the critic loss is +inf in minibatch 0, the block holds NaN and infinities; the sub-block build gives the
+    same words (same_words: x86 gives every NaN as 0xFFC00000, so here the bits are equal as well)"""
+    _, P, losses, grads = S.range_run("D-overflow")
+    print("D-overflow: %d NaN words and %d infinities in the block, losses %s" % (S.count_nan(P), int(np.isinf(P).sum()), losses.tolist()))
+    assert losses[0, 0] == np.inf and S.count_nan(P) >= 1 and int(np.isinf(P).sum()) >= 1
+    _, P2, l2, g2 = S.range_run("D-overflow", lib=SUB)
+    assert S.same_words(P, P2) and S.same_words(losses, l2) and S.same_words(grads, g2)
+    assert not S.same_words(P, S.range_start("D-overflow"))
+
+
+# ---- B. below the underflow the header is exactly scale-equivariant
+@pytest.mark.parametrize("library", [None, SUB])
+@pytest.mark.parametrize("s", [20, 40])
+def test_scaled_head_is_exactly_equivariant(s, library):
+    """w3, b3 of the critic and the targets times 2^-s: Q, dQ and the gradients of w3 and b3 carry 2^-s, every critic gradient
+    upstream (dQ * w3 first) 2^-2s, the critic loss 2^-2s -- exactly, every operation of the header being a correctly rounded
+    + - * / fmaf or sqrtf on operands scaled by a power of two, as long as nothing leaves the normal range.  First minibatch of a
+    call only: Adam is not scale-equivariant (epsilon; sqrt(v)), so the second minibatch meets another critic.
+    The actor side: the actor loss is -mean Q of the UPDATED critic, which is linear in (w3, b3), so it and every actor gradient
+    carry 2^-s exactly IF the two critics are the same function up to the head's scale.  Behind Adam's step with the reference's
+    critic_lr they are not (w -= m alpha / (sqrt(v) + epsilon) moves the scaled and the unscaled critic differently), so the
+    exponent is asserted with critic_lr = 0, which leaves both critics where they were (w -= 0 / (..) is exact)."""
+    lib = S.shim(library) if library else None
+    res = {}
+    for e in (0, s):
+        for lr in (S.HYPER["critic_lr"], 0.0):
+            P = S.host_block(S.scaled_head(e))
+            res[e, lr] = S.host_step(P, *S.scaled_minibatches(65, 1, 5, e), lib=lib, critic_lr=lr)
+    scaled = lambda x, k: np.ldexp(x, -k * s).astype(np.float32)                          # noqa: E731
+    for lr in (S.HYPER["critic_lr"], 0.0):
+        (l0, g0), (ls, gs) = res[0, lr], res[s, lr]
+        a, b = S.split_grads(g0[0]), S.split_grads(gs[0])
+        for k in a:
+            if k.startswith("critic/"):
+                assert np.any(a[k] != 0) and np.array_equal(S.bits32(b[k]), S.bits32(scaled(a[k], 1 if k in ("critic/w3", "critic/b3") else 2))), (k, lr)
+            elif lr == 0.0:
+                assert np.any(a[k] != 0) and np.array_equal(S.bits32(b[k]), S.bits32(scaled(a[k], 1))), k
+        assert np.array_equal(S.bits32(ls[0, 0]), S.bits32(scaled(l0[0, 0], 2)))
+        if lr == 0.0:
+            assert np.array_equal(S.bits32(ls[0, 1]), S.bits32(scaled(l0[0, 1], 1)))
+
+
+# ---- A at s = 62 and 70, F: the header against the semantics, by the rule of section 2
+def test_recorded_subnormal_spread_is_current():
+    """the figure behind SUBNORMAL_BAR, measured again (the one behind HEADER_BAR: test_recorded_spread_is_current, which
+    measures on these scenarios too)"""
+    worst, where = S.measure_f32_spread(subnormal=True)
+    print("LearnerModel(float32) against float64, tensors with a subnormal largest entry: %.3e at %s (recorded %.3e)"
+          % (worst, where, S.F32_SPREAD_SUBNORMAL_MEASURED))
+    assert where is not None and worst <= S.SUBNORMAL_BAR
+    worst, where = S.measure_f32_spread([b[0] for b in S.range_header_batches()])
+    print("LearnerModel(float32) against float64 on the range scenarios, all other tensors: %.3e at %s (recorded %.3e)"
+          % (worst, where, S.F32_SPREAD_MEASURED))
+    assert worst <= S.F32_SPREAD_MEASURED                      # below the record: it needs no constant of its own
+
+
+@pytest.mark.parametrize("label", [b[0] for b in S.range_header_batches()])
+def test_host_build_follows_the_model_in_the_range(label):
+    """as test_host_build_follows_the_model: gradients (per tensor) and losses within HEADER_BAR of LearnerModel(float64) -- within
+    SUBNORMAL_BAR for a tensor whose largest entry is itself subnormal (learner_scenarios.header_bar)"""
+    networks, (rows, act7, target) = S.header_inputs(label)
+    P = S.host_block(networks)
+    worst = {False: 0.0, True: 0.0}
+    for s in range(len(rows)):
+        l64, g64 = S.model(P, np.float64).step(rows[s], act7[s], target[s])
+        lh, gh = S.host_step(P, rows[s], act7[s], target[s])
+        got, ref = S.split_grads(gh[0]), S.split_grads(g64)
+        got.update(critic_loss=lh[0][0], actor_loss=lh[0][1])
+        ref.update(critic_loss=l64[0], actor_loss=l64[1])
+        for k in got:
+            d, sub = S.rel_dev(got[k], ref[k]), S.is_subnormal_tensor(ref[k])
+            worst[sub] = max(worst[sub], d)
+            assert d <= S.header_bar(ref[k]), (label, s, k, d)
+    print("%s: host build against LearnerModel(float64), worst tensor %.3e (bar %.3e); with a subnormal largest entry %.3e (bar %.3e)"
+          % (label, worst[False], S.HEADER_BAR, worst[True], S.SUBNORMAL_BAR))
+
+
 # ------------------------------------------------------------------ 5. the C ABI on a backend without the kernel
 def _emulators():
     from tests import rank_pairs_scenarios, test_capacity256

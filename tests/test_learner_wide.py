@@ -137,6 +137,47 @@ def test_sub_block_sizes_change_no_bit(bsz):
     assert np.array_equal(S.bits32(p1[:, used]), S.bits32(p2[:, used])) and np.all(np.isfinite(p1[:, used]))
 
 
+# ------------------------------------------------------------------ 3b. the float32 range (learner_scenarios: families A .. F)
+WIDE_SUB = "liblearner_wide_host_sub.so"
+
+
+def test_long_run_state_in_calls_and_across_builds():
+    """family C for the wide build: 40 steps of 130 rows (two slices, the second of 2 rows) from the state of step 850 of the long
+    run, where b1p is subnormal and still moving: one call == calls of 10 == the sub-block build"""
+    start = S.long_run()[S.LONG_MOVING]
+    rows, act7, target = W.minibatches(130, 40, seed=17)
+    blocks = []
+    for call, lib in ((40, None), (10, None), (40, W.shim(WIDE_SUB))):
+        P = start.copy()
+        for a in range(0, 40, call):
+            W.host_step_wide(P, rows[a:a + call], act7[a:a + call], target[a:a + call], want=False, lib=lib)
+        blocks.append(P)
+    P = blocks[0]
+    print("wide, steps 850 .. 890: b1p %.6e -> %.6e" % (start[LN.POWERS], P[LN.POWERS]))
+    assert S.B1P_FIXED_POINT < P[LN.POWERS] < start[LN.POWERS] < S.TINY and np.all(np.isfinite(P))
+    assert int(P[LN.STEPS:LN.STEPS + 1].view(np.int32)[0]) == S.LONG_MOVING + 40
+    assert np.array_equal(S.bits32(blocks[1]), S.bits32(P)) and np.array_equal(S.bits32(blocks[2]), S.bits32(P))
+
+
+@pytest.mark.parametrize("name", list(S.RANGE_CASES))
+def test_range_cases_keep_their_words_across_builds(name):
+    """every case of the range at 130 rows: finite (D: NaN and infinities, compared by same_words), and the same words from the
+    sub-block build; family A keeps its thousands of subnormal words at this batch"""
+    c = S.range_case(name)
+    _, P, losses, grads = W.range_run(name, 130)
+    _, P2, l2, g2 = W.range_run(name, 130, lib=WIDE_SUB)
+    for what, a, b in (("block", P, P2), ("losses", losses, l2), ("grads", grads, g2)):
+        S.check_words(a, b, "%s, %s of the sub-block build" % (name, what), nan_ok=c["nan_ok"])
+    if c["nan_ok"]:
+        assert losses[0, 0] == np.inf and S.count_nan(P) >= 1 and int(np.isinf(P).sum()) >= 1
+    else:
+        assert np.all(np.isfinite(P)) and np.all(np.isfinite(grads)) and np.all(np.isfinite(losses))
+    if c["family"] == "A":
+        n = S.count_subnormal(grads) + S.count_subnormal(P[:LN.STEPS])
+        print("%s at 130 rows: %d subnormal words in the gradients and the block" % (name, n))
+        assert n >= 1000
+
+
 # ------------------------------------------------------------------ 4. the wide header against the semantics
 def test_recorded_spread_is_current():
     """The figure behind the bar, measured again: the float32 model's spread stays below the bar derived from the record"""
