@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from ._args import is_tensor_of, tensor_in, tensor_out
 from ._capi import PveConfig, PveEnvInfo, PveOutputs, PveRollout, PveVehicle, PveError, check
 
 ALL_OUTPUTS = ("obs_post", "obs_pre", "reward", "flags", "lanej", "nbr", "new_slot", "env_out", "state_pre")
@@ -20,7 +21,7 @@ DEFAULT_OUTPUTS = ("obs_post", "reward", "flags", "nbr", "new_slot", "env_out")
 
 def make_config(lib, **kw):
     cfg = PveConfig()
-    lib.pve_default_config(C.byref(cfg))
+    lib.pve_default_config(C.byref(cfg))         # (no handle, no status: not a gateway call)
     for k, v in kw.items():
         if not hasattr(cfg, k):
             raise TypeError("unknown config field %r" % k)
@@ -73,7 +74,7 @@ class BatchedIntersections:
         self.cfg = make_config(self.lib, **config)
         self.lane_num = int(self.cfg.lane_num)
         self.dir_num = _capi.DIR_NUM.get(self.lane_num, 12)
-        nbytes = self.lib.pve_workspace_bytes(self.n_envs, self.capacity)
+        nbytes = self.lib.pve_workspace_bytes(self.n_envs, self.capacity)      # (a size query: no handle, no status)
         if nbytes == 0:
             raise PveError("invalid n_envs/capacity (capacity must be 64, 128 or 256; 256 needs lane_num 12)")
         self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
@@ -82,10 +83,11 @@ class BatchedIntersections:
         self._stream_obj = stream
         sptr = self._stream_ptr()
         h = C.c_void_p()
+        # (pve_create makes the handle the gateway passes, pve_destroy ends it: the two are called directly)
         check(self.lib, self.lib.pve_create(C.byref(self.cfg), self.n_envs, self.capacity, dev_index,
-                                            C.c_void_p(self.workspace.data_ptr()), sptr, C.byref(h)),
-              "pve_create")
+                                            self.workspace.data_ptr(), sptr, C.byref(h)), "pve_create")
         self._h = h
+        self._fns = {}                       # the gateway's bound entry points, by name
         self.arrivals = None
         if arrivals is not None:              # (None: generate_arrivals() will produce the stream on the device)
             self.set_arrivals(arrivals)
@@ -130,6 +132,32 @@ class BatchedIntersections:
             return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         return C.c_void_p(0)
 
+    def _bind_stream(self):
+        """THE stream rule: kernels follow torch's current stream unless the batch was created with its own `stream`, which
+        pve_create bound for good (nothing but pve_set_stream re-binds a handle, and nothing but this method calls it)."""
+        if self._stream_obj is None:
+            self.lib.pve_set_stream(self._h, self._stream_ptr())
+
+    def _call(self, name, *args, bind=True):
+        """THE gateway to the library: every entry point that takes the handle and returns a status is called here, by name.
+        Binds the stream by _bind_stream's rule, passes the handle first, a tensor as its data_ptr(), a ctypes structure by
+        reference and everything else (None = a null pointer) as it is, and raises PveError(name ...) on a status other than 0.
+        `args` keeps the tensors alive across the call.  bind=False: calls that launch nothing -- they wait for, read back or
+        describe what earlier calls enqueued, or set host state -- and so leave the handle on the stream that work went to.
+        Not through here, each with its reason where it stands: pve_create / pve_destroy, the queries that take no handle or
+        return no status, and the stepping calls (step, step_with_actor, step_many and prepare_step_many's callable), whose
+        host cost per tick is what bench.py times: the gateway costs more per call than those vary from run to run
+        (profiles/binding_gateway.txt), so they call their entry points directly, after the same _bind_stream()."""
+        fn = self._fns.get(name)
+        if fn is None:
+            fn = self._fns[name] = getattr(self.lib, name)      # (an unknown name: AttributeError, here)
+        if bind:
+            self._bind_stream()
+        rc = fn(self._h, *[a.data_ptr() if isinstance(a, torch.Tensor) else C.byref(a) if isinstance(a, C.Structure) else a
+                           for a in args])
+        if rc != 0:
+            check(self.lib, rc, name)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
             self.lib.pve_destroy(self._h)
@@ -146,8 +174,7 @@ class BatchedIntersections:
                             dtype=torch.float64)
         rows, stride_rows = self._stream_shape(a, "arrivals")
         self.arrivals = a.contiguous().to(self.device)
-        check(self.lib, self.lib.pve_set_arrivals(self._h, C.c_void_p(self.arrivals.data_ptr()), rows, stride_rows),
-              "pve_set_arrivals")
+        self._call("pve_set_arrivals", self.arrivals, rows, stride_rows, bind=False)
         self._is_reset = False
 
     def _stream_shape(self, a, what):
@@ -164,8 +191,7 @@ class BatchedIntersections:
         c = torch.as_tensor(np.asarray(choice) if not torch.is_tensor(choice) else choice, dtype=torch.int32)
         rows, stride_rows = self._stream_shape(c, "intentions")
         self.intentions = c.contiguous().to(self.device)
-        check(self.lib, self.lib.pve_set_intentions(self._h, C.c_void_p(self.intentions.data_ptr()), rows, stride_rows),
-              "pve_set_intentions")
+        self._call("pve_set_intentions", self.intentions, rows, stride_rows, bind=False)
         self._is_reset = False
 
     def generate_arrivals(self, rate, horizon_s=None, rows=None, seed=0, epoch=0, env_offset=0, min_gap=1.0, covered=False):
@@ -191,7 +217,6 @@ class BatchedIntersections:
         per_env = on_device or np.ndim(rate.cpu().numpy() if torch.is_tensor(rate) else rate) > 0
         g = _capi.PveArrivalGen(seed=int(seed) & 0xFFFFFFFFFFFFFFFF, env_offset=int(env_offset), epoch=int(epoch) & 0xFFFFFFFF, rows=rows,
                                 mean_s=1.0, mean_env=None, min_gap_s=float(min_gap), block_threads=0)
-        self._bind_stream()
         with self._own_stream():
             mean = None
             if on_device:
@@ -210,17 +235,14 @@ class BatchedIntersections:
                 buf["intentions"] = torch.empty(E, rows, ln, dtype=torch.int32, device=self.device) if ln == 8 else None
             arr, ch = buf["arrivals"], buf["intentions"]
             cov = torch.empty(E, dtype=torch.float64, device=self.device) if covered else None
-            check(self.lib, self.lib.pve_generate_arrivals(self._h, C.byref(g), C.c_void_p(arr.data_ptr()),
-                                                           C.c_void_p(ch.data_ptr()) if ch is not None else None,
-                                                           C.c_void_p(cov.data_ptr()) if cov is not None else None),
-                  "pve_generate_arrivals")
+            self._call("pve_generate_arrivals", g, arr, ch, cov)
             if mean is not None and self._stream_obj is not None and mean.is_cuda:
                 mean.record_stream(self._stream_obj)
         self.arrivals = arr
-        check(self.lib, self.lib.pve_set_arrivals(self._h, C.c_void_p(arr.data_ptr()), rows, rows), "pve_set_arrivals")
+        self._call("pve_set_arrivals", arr, rows, rows, bind=False)
         if ch is not None:
             self.intentions = ch
-            check(self.lib, self.lib.pve_set_intentions(self._h, C.c_void_p(ch.data_ptr()), rows, rows), "pve_set_intentions")
+            self._call("pve_set_intentions", ch, rows, rows, bind=False)
         self._is_reset = False
         return cov
 
@@ -228,7 +250,7 @@ class BatchedIntersections:
         """Zero-copy [n_envs, capacity] view of a persistent per-slot field (see pve_state_field)."""
         p = C.c_void_p()
         eb = C.c_int()
-        check(self.lib, self.lib.pve_state_field(self._h, name.encode(), C.byref(p), C.byref(eb)), "pve_state_field")
+        self._call("pve_state_field", name.encode(), C.byref(p), C.byref(eb), bind=False)
         off = p.value - self.workspace.data_ptr()
         n = self.n_envs * self.capacity * eb.value
         dt = torch.float64 if eb.value == 8 else torch.int32
@@ -246,8 +268,7 @@ class BatchedIntersections:
     def reset(self):
         """New episode: the reference builds a new TrafficInteraction (main.py:394) whose constructor
         warms up until the first vehicle exists (ref :214-220)."""
-        self.lib.pve_set_stream(self._h, self._stream_ptr())
-        check(self.lib, self.lib.pve_reset(self._h), "pve_reset")
+        self._call("pve_reset")
         if self._obs is not None:
             for o in self._obs:
                 o.zero_()
@@ -278,11 +299,6 @@ class BatchedIntersections:
             self.__dict__.setdefault("_out_dicts", {})[self._obs_cur] = d
         return o
 
-    def _bind_stream(self):
-        """Kernels follow torch's current stream unless the batch was created with its own `stream`."""
-        if self._stream_obj is None:
-            self.lib.pve_set_stream(self._h, self._stream_ptr())
-
     def _own_stream(self):
         """Context in which torch's allocations / fills / copies are ordered with this handle's kernels: the handle's own
         stream when it has one (a torch side stream is non-blocking: nothing else orders a `torch.zeros` or `copy_` on
@@ -299,7 +315,7 @@ class BatchedIntersections:
         assert a.dtype == torch.float64 and a.is_contiguous() and a.shape == (self.n_envs, self.capacity)
         self._bind_stream()
         o = self._outputs_struct(flip_obs=True)
-        rc = self.lib.pve_step_all(self._h, a.data_ptr(), C.byref(o))
+        rc = self.lib.pve_step_all(self._h, a.data_ptr(), C.byref(o))      # (a stepping call: direct, see _call)
         if rc != 0:
             check(self.lib, rc, "pve_step_all")
         self.ticks += 1
@@ -321,9 +337,8 @@ class BatchedIntersections:
         with self._own_stream():
             self._actor_w = w.to(self.device)
             self._actor_actions = torch.zeros(self.n_envs, self.capacity, dtype=torch.float64, device=self.device)
-            self._bind_stream()
             # copied into the handle's workspace (flat + packed for the matrix cores) on the handle's stream
-            check(self.lib, self.lib.pve_set_actor(self._h, C.c_void_p(self._actor_w.data_ptr())), "pve_set_actor")
+            self._call("pve_set_actor", self._actor_w)
 
     def set_exploration(self, sigma, seed=0, env_offset=0):
         """Exploration noise of the device actor (main.py:44, :239): from the next call on, every controlled vehicle's action
@@ -331,8 +346,7 @@ class BatchedIntersections:
         z = noise.action_noise(seed, env + env_offset, vehicle id, ticks since reset()) -- reproducible, and the same in
         every launch form.  sigma = 0 (the default state) switches it off.  env_offset: global index of this batch's first
         environment when the batch is a piece of a larger one.  Actions passed to step() are never touched."""
-        check(self.lib, self.lib.pve_set_action_noise(self._h, float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset)),
-              "pve_set_action_noise")
+        self._call("pve_set_action_noise", float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), bind=False)
         self.exploration = (float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset))
 
     # ------------------------------------------------------------------ target networks: critic and bootstrap Q
@@ -357,39 +371,27 @@ class BatchedIntersections:
                 if t.numel() != n:
                     raise PveError("%s needs %d float32 weights, got %d" % (what, n, t.numel()))
                 ptr.append(t.to(self.device))
-            self._bind_stream()
-            check(self.lib, self.lib.pve_set_target_networks(self._h, *[C.c_void_p(t.data_ptr() if t is not None else 0) for t in ptr]),
-                  "pve_set_target_networks")
+            self._call("pve_set_target_networks", *ptr)
             self._target_w = [t if t is not None else old for t, old in zip(ptr, getattr(self, "_target_w", [None, None]))]
 
     def _rows_arg(self, x, tail, what):
         """A contiguous device tensor of the handle's observation type whose trailing dimensions are `tail` -> (tensor, rows)"""
-        if not torch.is_tensor(x):
-            x = torch.as_tensor(np.asarray(x))
-        x = x.to(device=self.device, dtype=self.obs_dtype).contiguous()
-        if tuple(x.shape[-len(tail):]) != tail or x.numel() == 0:
-            raise PveError("%s must be [..., %s] and not empty" % (what, ", ".join(str(t) for t in tail)))
+        x = tensor_in(x, self.device, self.obs_dtype, tail, "%s must be [..., %s] and not empty" % (what, ", ".join(str(t) for t in tail)),
+                      tail=True)
         return x, x.numel() // int(np.prod(tail))
 
     def _f32_out(self, out, shape, what):
-        if out is None:
-            return torch.empty(shape, dtype=torch.float32, device=self.device)
-        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != int(np.prod(shape)) or out.device.type != self.device.type:
-            raise PveError("%s must be a contiguous float32 device tensor of %d elements" % (what, int(np.prod(shape))))
-        return out
+        return tensor_out(out, self.device, torch.float32, shape,
+                          "%s must be a contiguous float32 device tensor of %d elements" % (what, int(np.prod(shape))))
 
     def critic_q(self, rows, act7, out=None):
         """Q of the installed critic (main.py:76 `agent.Q(state, action, other_action)`): rows [..., 28] (the handle's
         observation type), act7 [..., 7] float32 (own action, then the six other actions) -> float32 [...] (device tensor)."""
         with self._own_stream():
             rows, n = self._rows_arg(rows, (28,), "rows")
-            a = (act7 if torch.is_tensor(act7) else torch.as_tensor(np.asarray(act7))).to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(a.shape) != tuple(rows.shape[:-1]) + (7,):
-                raise PveError("act7 must be [..., 7] with the leading shape of rows")
+            a = tensor_in(act7, self.device, torch.float32, tuple(rows.shape[:-1]) + (7,), "act7 must be [..., 7] with the leading shape of rows")
             q = self._f32_out(out, tuple(rows.shape[:-1]), "out")
-            self._bind_stream()
-            check(self.lib, self.lib.pve_critic_forward(self._h, C.c_void_p(rows.data_ptr()), C.c_void_p(a.data_ptr()),
-                                                        C.c_void_p(q.data_ptr()), n), "pve_critic_forward")
+            self._call("pve_critic_forward", rows, a, q, n)
         return q
 
     def bootstrap_q(self, state=None, flags=None, out=None, actions_out=None):
@@ -409,15 +411,10 @@ class BatchedIntersections:
             state, n = self._rows_arg(state, (7, 28), "state")
             lead = tuple(state.shape[:-2])
             if flags is not None:
-                flags = (flags if torch.is_tensor(flags) else torch.as_tensor(np.asarray(flags))).to(device=self.device, dtype=torch.int32).contiguous()
-                if tuple(flags.shape) != lead:
-                    raise PveError("flags must have the leading shape of state")
+                flags = tensor_in(flags, self.device, torch.int32, lead, "flags must have the leading shape of state")
             q = self._f32_out(out, lead, "out")
             a7 = self._f32_out(actions_out, lead + (7,), "actions_out")
-            self._bind_stream()
-            check(self.lib, self.lib.pve_bootstrap_q(self._h, C.c_void_p(state.data_ptr()),
-                                                     C.c_void_p(flags.data_ptr() if flags is not None else 0),
-                                                     C.c_void_p(q.data_ptr()), C.c_void_p(a7.data_ptr()), n), "pve_bootstrap_q")
+            self._call("pve_bootstrap_q", state, flags, q, a7, n)
         return q, a7
 
     # ------------------------------------------------------------------ n-step transitions (pve_nstep_scan / pve_nstep_gather)
@@ -434,7 +431,7 @@ class BatchedIntersections:
         keep = []
         for k in self._NSTEP_KEYS:
             tns = blocks[k]
-            if tuple(tns.shape) != want[k][0] or tns.dtype != want[k][1] or tns.device.type != self.device.type:
+            if not is_tensor_of(tns, want[k][1], self.device, shapes=(want[k][0],)):
                 raise PveError("nstep_transitions: %s[%r] must be a %s device tensor of shape %s" % (what, k, want[k][1], want[k][0]))
             tns = tns.contiguous()
             keep.append(tns)
@@ -494,9 +491,8 @@ class BatchedIntersections:
                 ns.obs_first = obs_first.data_ptr()
             if q is None:
                 q, _ = self.bootstrap_q(cur["state_pre"], cur["flags"])
-            q = q.to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(q.shape) != (n_cur, self.n_envs, self.capacity):
-                raise PveError("nstep_transitions: q must be [n_ticks, n_envs, capacity]")
+            q = tensor_in(q, self.device, torch.float32, (n_cur, self.n_envs, self.capacity),
+                          "nstep_transitions: q must be [n_ticks, n_envs, capacity]", convert=False)
             n_cand = min(n_prev, window - 1) + n_cur
             dev = self.device
             target = torch.empty(n_cand, self.n_envs, self.capacity, dtype=torch.float64, device=dev)
@@ -506,8 +502,7 @@ class BatchedIntersections:
             ns.gamma, ns.window, ns.mode = float(gamma), window, (_capi.NSTEP_TAIL if tail else 0)
             ns.q_boot, ns.target, ns.code, ns.offsets, ns.total = q.data_ptr(), target.data_ptr(), code.data_ptr(), offsets.data_ptr(), total.data_ptr()
             ns.block_threads = int(block_threads)
-            self._bind_stream()
-            check(self.lib, self.lib.pve_nstep_scan(self._h, C.byref(ns)), "pve_nstep_scan")
+            self._call("pve_nstep_scan", ns)
             if max_records is None:
                 n_out = total_out = int(total.item())
             else:
@@ -515,16 +510,14 @@ class BatchedIntersections:
             records = torch.empty(n_out, _capi.NSTEP_RECORD, dtype=torch.float32, device=dev)
             index = torch.empty(n_out, 4, dtype=torch.int32, device=dev)
             ns.max_records, ns.records, ns.index = n_out, records.data_ptr(), index.data_ptr()
-            check(self.lib, self.lib.pve_nstep_gather(self._h, C.byref(ns)), "pve_nstep_gather")
+            self._call("pve_nstep_gather", ns)
             self._nstep_last = (target, code, offsets)      # (diagnostics: the dense scan outputs of the last call)
         return records, index, total_out
 
     def act(self):
         """actions [n_envs, capacity] = actor(obs) for the controlled slots (+ the exploration noise, set_exploration),
         0 elsewhere (device tensor)."""
-        self.lib.pve_set_stream(self._h, self._stream_ptr())
-        check(self.lib, self.lib.pve_actor_forward(self._h, None, C.c_void_p(self.obs.data_ptr()),
-                                                   C.c_void_p(self._actor_actions.data_ptr())), "pve_actor_forward")
+        self._call("pve_actor_forward", None, self.obs, self._actor_actions)
         return self._actor_actions
 
     def step_with_actor(self):
@@ -533,9 +526,8 @@ class BatchedIntersections:
         self._bind_stream()
         obs_in = self._obs[self._obs_cur]
         o = self._outputs_struct(flip_obs=True)
-        check(self.lib, self.lib.pve_step_all_actor(self._h, None, C.c_void_p(obs_in.data_ptr()),
-                                                    C.c_void_p(self._actor_actions.data_ptr()), C.byref(o)),
-              "pve_step_all_actor")
+        check(self.lib, self.lib.pve_step_all_actor(self._h, None, obs_in.data_ptr(), self._actor_actions.data_ptr(), C.byref(o)),
+              "pve_step_all_actor")                                          # (a stepping call: direct, see _call)
         self.ticks += 1
         return self.outputs()
 
@@ -629,7 +621,7 @@ class BatchedIntersections:
             raise PveError("step_many: state_pre needs a trajectory roll-out (every tick reads the rows the previous one stored)")
         if not trajectory:
             o = self._outputs_struct(flip_obs=False)
-            check(self.lib, self.lib.pve_step_many(self._h, C.byref(ro), C.byref(o)), "pve_step_many")
+            check(self.lib, self.lib.pve_step_many(self._h, C.byref(ro), C.byref(o)), "pve_step_many")     # (a stepping call: direct, see _call)
             self.ticks += n_ticks
             return self._out_dicts[self._obs_cur]
         o = PveOutputs()
@@ -650,7 +642,7 @@ class BatchedIntersections:
                 o.obs_prev_post = self._obs[self._obs_cur].data_ptr()
                 if not update_views:
                     raise PveError("step_many with state_pre reads the handle's observation view: update_views must stay True")
-            check(self.lib, self.lib.pve_step_many(self._h, C.byref(ro), C.byref(o)), "pve_step_many")
+            check(self.lib, self.lib.pve_step_many(self._h, C.byref(ro), C.byref(o)), "pve_step_many")     # (as above)
             self.ticks += n_ticks
             obs_first = self._obs[self._obs_cur] if self._obs is not None else None   # the rows stored before this call
             if n_ticks > 0 and update_views:     # the handle's single-tick views keep showing the latest tick
@@ -697,6 +689,7 @@ class BatchedIntersections:
             raise PveError("unknown action source %r" % (source,))
         self._bind_stream()
         o = self._outputs_struct(flip_obs=False)
+        # (the prepared call runs no gateway code: the entry point and its arguments are bound here, once)
         fn, h, pro, po, n_pool = self.lib.pve_step_many, self._h, C.byref(ro), C.byref(o), max(1, int(ro.n_pool))
         src_attr = {"pool": "_pool", "table": "_table"}.get(source)
         src_tensor = getattr(self, src_attr) if src_attr else None
@@ -720,29 +713,25 @@ class BatchedIntersections:
         """Split protocol, part 1: all step() calls + scene_update(); Done vehicles stay in place."""
         a = self._zero_actions if actions is None else actions
         assert a.dtype == torch.float64 and a.is_contiguous() and a.shape == (self.n_envs, self.capacity)
-        self.lib.pve_set_stream(self._h, self._stream_ptr())
-        o = self._outputs_struct(flip_obs=True)
-        check(self.lib, self.lib.pve_scene_update(self._h, C.c_void_p(a.data_ptr()), C.byref(o)), "pve_scene_update")
+        self._call("pve_scene_update", a, self._outputs_struct(flip_obs=True))
         self.ticks += 1
         return self.outputs()
 
     def compact(self):
         """Split protocol, part 2: delete_vehicle() (ref :435)."""
-        self.lib.pve_set_stream(self._h, self._stream_ptr())
-        obs = C.c_void_p(self._obs[self._obs_cur].data_ptr()) if self._obs is not None else C.c_void_p(0)
-        check(self.lib, self.lib.pve_compact(self._h, obs), "pve_compact")
+        self._call("pve_compact", self._obs[self._obs_cur] if self._obs is not None else None)
 
     def outputs(self):
         self._outputs_struct(flip_obs=False)
         return self._out_dicts[self._obs_cur]
 
     def synchronize(self):
-        check(self.lib, self.lib.pve_synchronize(self._h), "pve_synchronize")
+        self._call("pve_synchronize", bind=False)
 
     def last_launch(self):
         """What the last stepping call launched: "tick" (one launch per tick), "resident" (one k_rollout launch per chunk),
         "persistent" (one launch for the call, items pulled from the work queue) or "none" (pve_debug_last_launch)."""
-        k = self.lib.pve_debug_last_launch(self._h)
+        k = self.lib.pve_debug_last_launch(self._h)        # (returns the kind, not a status: not a gateway call)
         if k < 0 or k > 3:                              # (a negative PVE_ERR_* must not index the tuple from its end)
             check(self.lib, k if k < 0 else -1, "pve_debug_last_launch")
         return _capi.LAUNCH_NAMES[k]
@@ -756,7 +745,7 @@ class BatchedIntersections:
         v = _capi.PveLaunchVariant()
         if not hasattr(self.lib, "pve_debug_last_variant"):
             raise PveError("this library is an older build: it lacks pve_debug_last_variant (rebuild it)")
-        check(self.lib, self.lib.pve_debug_last_variant(self._h, C.byref(v)), "pve_debug_last_variant")
+        self._call("pve_debug_last_variant", v, bind=False)
         d = {n: int(getattr(v, n)) for n, _t in _capi.PveLaunchVariant._fields_ if n != "reserved"}
         d["kind"] = _capi.LAUNCH_NAMES[d["kind"]]
         return d
@@ -764,19 +753,19 @@ class BatchedIntersections:
     # ------------------------------------------------------------------ host read-back
     def read_env(self, env=0):
         info = PveEnvInfo()
-        check(self.lib, self.lib.pve_read_env(self._h, env, C.byref(info)), "pve_read_env")
+        self._call("pve_read_env", env, info, bind=False)
         return info
 
     def read_vehicles(self, env=0):
         buf = (PveVehicle * self.capacity)()
         n = C.c_int()
-        check(self.lib, self.lib.pve_read_vehicles(self._h, env, buf, self.capacity, C.byref(n)), "pve_read_vehicles")
+        self._call("pve_read_vehicles", env, buf, self.capacity, C.byref(n), bind=False)
         return [buf[i] for i in range(min(n.value, self.capacity))]
 
     def metrics(self):
         """dict of the 12 metric sums over this handle's envs since reset (SURVEY §8e vector)."""
         out = (C.c_double * _capi.PVE_N_METRICS)()
-        check(self.lib, self.lib.pve_get_metrics(self._h, out), "pve_get_metrics")
+        self._call("pve_get_metrics", out, bind=False)
         return dict(zip(_capi.METRIC_NAMES, [float(x) for x in out]))
 
     # ------------------------------------------------------------------ statistics by group (pve_rollout_stats / pve_metrics_groups)
@@ -791,18 +780,11 @@ class BatchedIntersections:
             if torch.is_tensor(groups) and groups.device.type == "cuda":
                 raise PveError("%s: pass n_groups with a group map on the device" % what)
             n_groups = int(np.max(groups.numpy() if torch.is_tensor(groups) else np.asarray(groups))) + 1
-        g = (groups if torch.is_tensor(groups) else torch.as_tensor(np.asarray(groups))).to(device=self.device, dtype=torch.int32).contiguous()
-        if tuple(g.shape) != (self.n_envs,):
-            raise PveError("%s: groups must be [n_envs]" % what)
-        return g, int(n_groups)
+        return tensor_in(groups, self.device, torch.int32, (self.n_envs,), "%s: groups must be [n_envs]" % what), int(n_groups)
 
     def _f64_arg(self, x, shape, what):
-        if x is None:
-            return torch.empty(shape, dtype=torch.float64, device=self.device)
-        if not torch.is_tensor(x) or x.dtype != torch.float64 or not x.is_contiguous() or tuple(x.shape) != tuple(shape) or \
-                x.device.type != self.device.type:
-            raise PveError("%s must be a contiguous float64 device tensor of shape %s" % (what, tuple(shape)))
-        return x
+        return tensor_out(x, self.device, torch.float64, shape,
+                          "%s must be a contiguous float64 device tensor of shape %s" % (what, tuple(shape)), same_shape=True)
 
     def rollout_stats(self, traj=None, groups=None, n_groups=None, out=None, totals=None, block_threads=0):
         """The roll-out's statistics by tick and by group of environments (pve_rollout_stats; what main.py:286-304 writes per
@@ -833,8 +815,7 @@ class BatchedIntersections:
                 tns = traj.get(k)
                 if tns is None:
                     continue
-                if not torch.is_tensor(tns) or tns.dtype != dt or tns.device.type != self.device.type or \
-                        tuple(tns.shape) not in (shp, shp[1:] if T == 1 else shp) or T < 1:
+                if not is_tensor_of(tns, dt, self.device, shapes=(shp, shp[1:] if T == 1 else shp)) or T < 1:
                     raise PveError("rollout_stats: %s must be a %s device tensor of shape %s" % (k, dt, shp))
                 keep[k] = tns.contiguous()
             g, G = self._groups_arg(groups, n_groups, "rollout_stats")
@@ -849,8 +830,7 @@ class BatchedIntersections:
                                 reward=keep["reward"].data_ptr(), obs_pre=keep["obs_pre"].data_ptr() if "obs_pre" in keep else None,
                                 env_out=keep["env_out"].data_ptr(), series=series.data_ptr(),
                                 totals=totals.data_ptr() if totals is not None else None, scratch=rows.data_ptr())
-            self._bind_stream()
-            check(self.lib, self.lib.pve_rollout_stats(self._h, C.byref(st)), "pve_rollout_stats")
+            self._call("pve_rollout_stats", st)
             if self._stream_obj is not None and self.device.type == "cuda":
                 for tns in list(keep.values()) + ([g] if g is not None else []):
                     tns.record_stream(self._stream_obj)
@@ -864,9 +844,7 @@ class BatchedIntersections:
         with self._own_stream():
             g, G = self._groups_arg(groups, n_groups, "metrics_by_group")
             res = self._f64_arg(out, (G, _capi.PVE_N_METRICS), "out")
-            self._bind_stream()
-            check(self.lib, self.lib.pve_metrics_groups(self._h, C.c_void_p(g.data_ptr()) if g is not None else None, G,
-                                                        C.c_void_p(res.data_ptr())), "pve_metrics_groups")
+            self._call("pve_metrics_groups", g, G, res)
             if g is not None and self._stream_obj is not None and self.device.type == "cuda":
                 g.record_stream(self._stream_obj)
         return res

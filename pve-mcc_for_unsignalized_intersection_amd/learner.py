@@ -17,12 +17,10 @@ Not part of the step: td_error / update_priority (main.py:76-79, dead with rand_
 PrioritizedReplayMemory.update_priority (replay.py).  The summaries main.py:286-304 writes per tick, and the collision rate that
 keeps best.cptk (main.py:315-328), come from the roll-out's own outputs: BatchedIntersections.rollout_stats and stats.summaries
 (stats.py)."""
-import ctypes as C
-
 import numpy as np
 
 from . import _capi
-from ._capi import PveError, check
+from ._capi import PveError
 from .critic import KEYS, flat_critic_weights
 
 N_ACTOR, N_CRITIC = _capi.PVE_ACTOR_N_WEIGHTS, _capi.PVE_CRITIC_N_WEIGHTS
@@ -241,46 +239,38 @@ class Learner:
                 if torch.is_tensor(w):
                     w = w.detach().cpu().numpy()
                 nets.append(torch.from_numpy(flat_weights(w, crit)).to(batch.device))
-            self._call(batch.lib.pve_learner_init, "pve_learner_init", *[C.c_void_p(t.data_ptr() if t is not None else 0) for t in nets])
+            batch._call("pve_learner_init", self._lr, *nets)
             self._init_sources = nets                                         # (alive until the copy has run)
 
-    def _call(self, fn, what, *args):
-        b = self.batch
-        b._bind_stream()
-        check(b.lib, fn(b._h, C.byref(self._lr), *args), what)
+    def _minibatches(self, method, rows, act7, target, losses, grads, critic_only):
+        """The arguments `step` and `step_wide` share, checked and made contiguous -> (rows, act7, target, batch, n_batches,
+        [losses, grads]); sets the descriptor's flags.  Runs inside the batch's stream context."""
+        from ._args import is_tensor_of, tensor_out
+        torch, dev = self._torch, self.params.device
+        for x, what in ((rows, "rows"), (act7, "act7"), (target, "target")):
+            if not is_tensor_of(x, torch.float32, dev, same_device=True):
+                raise PveError("Learner.%s: %s must be a float32 tensor on %s" % (method, what, dev))
+        if rows.dim() == 2:
+            rows, act7, target = rows[None], act7[None], target[None]
+        if rows.dim() != 3 or rows.shape[2] != 28 or rows.shape[1] < 1 or rows.shape[0] < 1 or \
+                tuple(act7.shape) != tuple(rows.shape[:2]) + (7,) or tuple(target.shape) != tuple(rows.shape[:2]):
+            raise PveError("Learner.%s: rows [n_batches, batch, 28], act7 [.., 7] and target [..] are needed" % method)
+        n, B = int(rows.shape[0]), int(rows.shape[1])
+        outs = [None if o is None or o is False else
+                tensor_out(None if o is True else o, dev, torch.float32, (n, width),
+                           "Learner.%s: %s must be a contiguous float32 device tensor [%d, %d]" % (method, what, n, width), same_device=True)
+                for o, width, what in ((losses, 2, "losses"), (grads, N_GRADS, "grads"))]
+        self._lr.flags = CRITIC_ONLY if critic_only else 0
+        return rows.contiguous(), act7.contiguous(), target.contiguous(), B, n, outs
 
     def step(self, rows, act7, target, losses=None, grads=None, critic_only=False):
         """Run one learner step per minibatch, in order.  rows float32 [batch, 28] or [n_batches, batch, 28], act7 [.., 7],
         target [..]: device tensors as ReplayMemory.sample returns them.  losses: True or a float32 device tensor
         [n_batches, 2] to receive (critic loss, actor loss) per step; grads: True or a tensor [n_batches, 6841 + 6393] to
         receive the gradients each step applied.  Returns (losses, grads), None where not asked for.  Never synchronises."""
-        torch = self._torch
-        b = self.batch
-        with b._own_stream():
-            for x, what in ((rows, "rows"), (act7, "act7"), (target, "target")):
-                if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device != self.params.device:
-                    raise PveError("Learner.step: %s must be a float32 tensor on %s" % (what, self.params.device))
-            if rows.dim() == 2:
-                rows, act7, target = rows[None], act7[None], target[None]
-            if rows.dim() != 3 or rows.shape[2] != 28 or rows.shape[1] < 1 or rows.shape[0] < 1 or \
-                    tuple(act7.shape) != tuple(rows.shape[:2]) + (7,) or tuple(target.shape) != tuple(rows.shape[:2]):
-                raise PveError("Learner.step: rows [n_batches, batch, 28], act7 [.., 7] and target [..] are needed")
-            n, B = int(rows.shape[0]), int(rows.shape[1])
-            rows, act7, target = rows.contiguous(), act7.contiguous(), target.contiguous()
-            outs = []
-            for o, width, what in ((losses, 2, "losses"), (grads, N_GRADS, "grads")):
-                if o is None or o is False:
-                    outs.append(None)
-                elif o is True:
-                    outs.append(torch.empty(n, width, dtype=torch.float32, device=self.params.device))
-                else:
-                    if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.numel() != n * width or \
-                            o.device != self.params.device:
-                        raise PveError("Learner.step: %s must be a contiguous float32 device tensor [%d, %d]" % (what, n, width))
-                    outs.append(o)
-            self._lr.flags = CRITIC_ONLY if critic_only else 0
-            self._call(b.lib.pve_learner_step, "pve_learner_step", C.c_void_p(rows.data_ptr()), C.c_void_p(act7.data_ptr()),
-                       C.c_void_p(target.data_ptr()), B, n, *[C.c_void_p(o.data_ptr() if o is not None else 0) for o in outs])
+        with self.batch._own_stream():
+            rows, act7, target, B, n, outs = self._minibatches("step", rows, act7, target, losses, grads, critic_only)
+            self.batch._call("pve_learner_step", self._lr, rows, act7, target, B, n, *outs)
         return outs[0], outs[1]
 
     def step_wide(self, rows, act7, target, losses=None, grads=None, critic_only=False, groups=0):
@@ -290,39 +280,14 @@ class Learner:
         different, equally fixed order of summation that depends on the batch size alone.  groups: workgroups of the slice
         passes, 0 = one per slice up to the device's compute units (no result depends on it).  The workspace is allocated on the
         batch's stream, kept, and grown with the batch.  Never synchronises."""
-        torch = self._torch
-        b = self.batch
-        with b._own_stream():
-            for x, what in ((rows, "rows"), (act7, "act7"), (target, "target")):
-                if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device != self.params.device:
-                    raise PveError("Learner.step_wide: %s must be a float32 tensor on %s" % (what, self.params.device))
-            if rows.dim() == 2:
-                rows, act7, target = rows[None], act7[None], target[None]
-            if rows.dim() != 3 or rows.shape[2] != 28 or rows.shape[1] < 1 or rows.shape[0] < 1 or \
-                    tuple(act7.shape) != tuple(rows.shape[:2]) + (7,) or tuple(target.shape) != tuple(rows.shape[:2]):
-                raise PveError("Learner.step_wide: rows [n_batches, batch, 28], act7 [.., 7] and target [..] are needed")
-            n, B = int(rows.shape[0]), int(rows.shape[1])
-            rows, act7, target = rows.contiguous(), act7.contiguous(), target.contiguous()
-            outs = []
-            for o, width, what in ((losses, 2, "losses"), (grads, N_GRADS, "grads")):
-                if o is None or o is False:
-                    outs.append(None)
-                elif o is True:
-                    outs.append(torch.empty(n, width, dtype=torch.float32, device=self.params.device))
-                else:
-                    if not torch.is_tensor(o) or o.dtype != torch.float32 or not o.is_contiguous() or o.numel() != n * width or \
-                            o.device != self.params.device:
-                        raise PveError("Learner.step_wide: %s must be a contiguous float32 device tensor [%d, %d]" % (what, n, width))
-                    outs.append(o)
+        with self.batch._own_stream():
+            rows, act7, target, B, n, outs = self._minibatches("step_wide", rows, act7, target, losses, grads, critic_only)
             need = wide_floats(B)
             work = getattr(self, "_wide_work", None)
             if work is None or work.numel() < need:
                 # (never zeroed: every float a launch reads was written by an earlier launch of the same call)
-                work = self._wide_work = torch.empty(need, dtype=torch.float32, device=self.params.device)
-            self._lr.flags = CRITIC_ONLY if critic_only else 0
-            self._call(b.lib.pve_learner_step_wide, "pve_learner_step_wide", C.c_void_p(rows.data_ptr()), C.c_void_p(act7.data_ptr()),
-                       C.c_void_p(target.data_ptr()), B, n, C.c_void_p(work.data_ptr()), work.numel(), int(groups),
-                       *[C.c_void_p(o.data_ptr() if o is not None else 0) for o in outs])
+                work = self._wide_work = self._torch.empty(need, dtype=self._torch.float32, device=self.params.device)
+            self.batch._call("pve_learner_step_wide", self._lr, rows, act7, target, B, n, work, work.numel(), int(groups), *outs)
         return outs[0], outs[1]
 
     # ---- views of the block, in the layouts set_actor / set_target_networks take

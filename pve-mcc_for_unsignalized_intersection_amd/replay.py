@@ -10,12 +10,10 @@ Ring: record number w (0-based over all adds) lives in slot w mod capacity; the 
 L = min(written, capacity); age index a in [0, L) names record written - L + a (0 = the oldest, the deque's left end).
 Draw: minibatch number d (draws, draws + 1, ..) takes the age indices perm(seed, d, L)(j), j = 0 .. batch_size - 1.  The
 reference's Mersenne-Twister draw (random.sample) is not reproduced; like the exploration noise the draw is this library's own."""
-import ctypes as C
-
 import numpy as np
 
 from . import _capi
-from ._capi import PveError, check
+from ._capi import PveError
 from .noise import philox4x32_10
 
 RECORD = 36
@@ -161,22 +159,18 @@ class ReplayMemory:
         self._rp.capacity, self._rp.store, self._rp.state = self.capacity, self.store.data_ptr(), self.state.data_ptr()
         self._rp.seed, self._rp.block_threads = self.seed, int(block_threads)
 
-    def _call(self, fn, what, *args):
-        b = self.batch
-        b._bind_stream()
-        check(b.lib, fn(b._h, C.byref(self._rp), *args), what)
-
     def reset(self):
         with self.batch._own_stream():
-            self._call(self.batch.lib.pve_replay_reset, "pve_replay_reset")
+            self.batch._call("pve_replay_reset", self._rp)
 
     def add(self, records, total=None):
         """Append records (float32 device tensor [n_max, 36], the output of nstep_transitions()) in order.  total: the 0-dim
         int64 device tensor nstep_transitions(max_records=...) returns -- the first min(total, n_max) records are appended, with
         no synchronisation -- or None for all n_max."""
+        from ._args import is_tensor_of
         torch = self._torch
         b = self.batch
-        if not torch.is_tensor(records) or records.dtype != torch.float32 or records.dim() != 2 or records.shape[1] != RECORD:
+        if not is_tensor_of(records, torch.float32) or records.dim() != 2 or records.shape[1] != RECORD:
             raise PveError("ReplayMemory.add: records must be a float32 device tensor [n, 36]")
         if records.device != self.store.device:              # (the full device: another GPU's pointer must not reach this launch)
             raise PveError("ReplayMemory.add: records are on %s, the memory is on %s" % (records.device, self.store.device))
@@ -186,8 +180,7 @@ class ReplayMemory:
                 if not torch.is_tensor(total):
                     total = torch.as_tensor(int(total), dtype=torch.int64)
                 total = total.to(device=b.device, dtype=torch.int64).reshape(1)
-            self._call(b.lib.pve_replay_append, "pve_replay_append", C.c_void_p(records.data_ptr()),
-                       C.c_void_p(total.data_ptr() if total is not None else 0), int(records.shape[0]))
+            b._call("pve_replay_append", self._rp, records, total, int(records.shape[0]))
 
     def sample(self, n_batches=1, check=True):
         """Draw n_batches minibatches of batch_size distinct live records -> (rows float32 [n_batches, batch_size, 28], act7
@@ -204,8 +197,7 @@ class ReplayMemory:
             act7 = torch.empty(n, B, 7, dtype=torch.float32, device=b.device)
             target = torch.empty(n, B, dtype=torch.float32, device=b.device)
             seq = torch.empty(n, B, dtype=torch.int64, device=b.device)
-            self._call(b.lib.pve_replay_sample, "pve_replay_sample", B, n, C.c_void_p(rows.data_ptr()), C.c_void_p(act7.data_ptr()),
-                       C.c_void_p(target.data_ptr()), C.c_void_p(seq.data_ptr()))
+            b._call("pve_replay_sample", self._rp, B, n, rows, act7, target, seq)
             if check:
                 L = int(self.state[STATUS].item())
                 if L < B:
@@ -408,7 +400,7 @@ class PrioritizedReplayMemory(ReplayMemory, _PrioConfig):
         self._torch = torch
         self.batch = batch
         self._configure(buffer_size, batch_size, seed, alpha, beta_zero, learn_start, steps, partition_num, PveError)
-        scratch_bytes = int(batch.lib.pve_prio_scratch_bytes(self.capacity))
+        scratch_bytes = int(batch.lib.pve_prio_scratch_bytes(self.capacity))          # (a size query: no handle, no status)
         self._ends_host = np.ascontiguousarray(self.ends, np.int32)
         self._part_from = np.ascontiguousarray(self.part_from, np.int64)
         with batch._own_stream():
@@ -430,20 +422,15 @@ class PrioritizedReplayMemory(ReplayMemory, _PrioConfig):
         p.scratch, p.scratch_bytes, p.ends, p.batch = self.scratch.data_ptr(), scratch_bytes, self.ends_dev.data_ptr(), self.batch_size
         p.ends_host, p.part_from = self._ends_host.ctypes.data, self._part_from.ctypes.data
 
-    def _pcall(self, fn, what, *args):
-        b = self.batch
-        b._bind_stream()
-        check(b.lib, fn(b._h, C.byref(self._pp), *args), what)
-
     def reset(self):
         with self.batch._own_stream():
-            self._call(self.batch.lib.pve_replay_reset, "pve_replay_reset")
-            self._pcall(self.batch.lib.pve_prio_reset, "pve_prio_reset")
+            self.batch._call("pve_replay_reset", self._rp)
+            self.batch._call("pve_prio_reset", self._pp)
 
     def rank(self):
         """Rank the live records -> order (int32 device tensor [capacity]; its first live() entries are the age indices by rank)"""
         with self.batch._own_stream():
-            self._pcall(self.batch.lib.pve_prio_rank, "pve_prio_rank")
+            self.batch._call("pve_prio_rank", self._pp)
         return self.order
 
     def sample(self, n_batches=1, beta=None, check=True):
@@ -463,8 +450,7 @@ class PrioritizedReplayMemory(ReplayMemory, _PrioConfig):
             seq = torch.empty(n, B, dtype=torch.int64, device=b.device)
             rank = torch.empty(n, B, dtype=torch.int32, device=b.device)
             weight = torch.empty(n, B, dtype=torch.float32, device=b.device)
-            self._pcall(b.lib.pve_prio_sample, "pve_prio_sample", n, self.min_live, C.c_float(float(ab)), *(C.c_void_p(t.data_ptr())
-                        for t in (rows, act7, target, seq, rank, weight)))
+            b._call("pve_prio_sample", self._pp, n, self.min_live, float(ab), rows, act7, target, seq, rank, weight)
             if check:
                 L = int(self.pstate[PLIVE].item())
                 if L < self.min_live:
@@ -474,15 +460,15 @@ class PrioritizedReplayMemory(ReplayMemory, _PrioConfig):
     def update_priority(self, seq, q, target=None):
         """Store |q - target| (|q| without a target) as the priority of the records `seq` names: int64 / float32 device tensors
         of equal element counts, e.g. sample()'s seq and target and critic_q(rows, act7)."""
+        from ._args import is_tensor_of
         torch = self._torch
         b = self.batch
         want = (("seq", seq, torch.int64), ("q", q, torch.float32)) + ((("target", target, torch.float32),) if target is not None else ())
-        for name, t, dt in want:
-            if not torch.is_tensor(t) or t.dtype != dt or t.device != self.store.device or t.numel() != seq.numel():
+        for name, t, dt in want:                             # (seq first: the others are counted against it)
+            if not is_tensor_of(t, dt, self.store.device, same_device=True) or t.numel() != seq.numel():
                 raise PveError("PrioritizedReplayMemory.update_priority: %s must be a %s tensor on %s with seq's element count"
                                % (name, dt, self.store.device))
         with b._own_stream():
             seq, q = seq.contiguous(), q.contiguous()
             target = target.contiguous() if target is not None else None
-            self._pcall(b.lib.pve_prio_update, "pve_prio_update", C.c_void_p(seq.data_ptr()), C.c_void_p(q.data_ptr()),
-                        C.c_void_p(target.data_ptr() if target is not None else 0), int(seq.numel()))
+            b._call("pve_prio_update", self._pp, seq, q, target, int(seq.numel()))
