@@ -1,5 +1,7 @@
 // pve_math_probe.hip -- the tick's small arithmetic helpers (csrc/pve_tick_core.h, pve_tick_geo.h, pve_actor.h), one
 // at a time, over caller-supplied arrays.  Test infrastructure only: tests/test_math_probe.py, tests/test_gpu_math_probe.py.
+// The last section does the same for the generators' and replay helpers' functions (pve_noise.h, pve_arrivals.h,
+// pve_replay.h, pve_prio.h): tests/test_gen_probe.py, tests/test_gpu_gen_probe.py.
 //
 // One source, two builds (tests/math_probe/Makefile):
 //   libpve_math_probe_hip.so   hipcc with the product's HIPFLAGS: every entry point launches ONE one-dimensional,
@@ -212,6 +214,120 @@ extern "C" int pve_probe_actor_tanh3(const pve_config *cfg, const pve_probe_args
 #else
     return PROBE_E_DEVICE_ONLY;      // v_exp_f32 / v_rcp_f32: no host form
 #endif
+}
+
+// ====================================================================================== generators and replay helpers
+// csrc/pve_noise.h, pve_arrivals.h, pve_replay.h, pve_prio.h (all reached through pve_host.h), one PVE_HD function per entry
+// point: tests/gen_probe_scenarios.py, tests/test_gen_probe.py, tests/test_gpu_gen_probe.py.  Scalars of the helpers that are
+// 64 bits wide or vary per element (seed, d, env_global, written, ..) are arrays, so that one call sweeps them; `bool`
+// arguments travel as int32.  Four output words are a row of an [n][4] array.  Two helpers have preconditions whose breach
+// would not end (replay_perm's walk for j >= N) or would trap the host (a capacity of 0 under `%`), and their arguments lie
+// in device memory where the host cannot look before the launch: those elements are answered with all ones instead of a call.
+typedef long long i64;
+struct B_philox4x32_10 {     // in: counter [n][4], key [n][2] -> out: [n][4]
+    PROBE_F(Const) {
+        uint32_t w[4];
+        for (int q = 0; q < 4; q++) w[q] = in<uint32_t>(a, 0)[4 * i + q];
+        philox4x32_10(w, in<uint32_t>(a, 1)[2 * i], in<uint32_t>(a, 1)[2 * i + 1]);
+        for (int q = 0; q < 4; q++) out<uint32_t>(a, 0)[4 * i + q] = w[q];
+    }
+};
+struct B_noise_gauss { PROBE_F(Const) { out<double>(a, 0)[i] = noise_gauss(in<uint32_t>(a, 0)[i], in<uint32_t>(a, 1)[i]); } };
+struct B_action_noise_z {    // in: seed, env_global, vehicle_id, tick
+    PROBE_F(Const) { out<double>(a, 0)[i] = action_noise_z(in<uint64_t>(a, 0)[i], in<int64_t>(a, 1)[i], in<int32_t>(a, 2)[i], in<uint32_t>(a, 3)[i]); }
+};
+struct B_action_with_noise { // in: a, sigma, seed, env_global, vehicle_id, tick
+    PROBE_F(Const) {
+        ActionNoise nz = {};
+        nz.sigma = in<double>(a, 1)[i]; nz.seed = in<uint64_t>(a, 2)[i];
+        out<double>(a, 0)[i] = action_with_noise(in<double>(a, 0)[i], nz, in<int64_t>(a, 3)[i], in<int32_t>(a, 4)[i], in<uint32_t>(a, 5)[i]);
+    }
+};
+struct B_arrival_exp { PROBE_F(Const) { out<double>(a, 0)[i] = arrival_exp(in<uint32_t>(a, 0)[i]); } };
+struct B_arrival_gap { PROBE_F(Const) { out<double>(a, 0)[i] = arrival_gap(in<uint32_t>(a, 0)[i], in<double>(a, 1)[i], in<double>(a, 2)[i]); } };
+#define PROBE_WORDS(fn)      /* in: seed, epoch, env_global, lane, quad | chunk -> out: [n][4] */                            \
+    PROBE_F(Const) {                                                                                                         \
+        uint32_t w[4];                                                                                                       \
+        fn(in<uint64_t>(a, 0)[i], in<uint32_t>(a, 1)[i], in<i64>(a, 2)[i], in<int>(a, 3)[i], in<uint32_t>(a, 4)[i], w);     \
+        for (int q = 0; q < 4; q++) out<uint32_t>(a, 0)[4 * i + q] = w[q];                                                   \
+    }
+struct B_arrival_words { PROBE_WORDS(arrival_words) };
+struct B_intention_words { PROBE_WORDS(intention_words) };
+struct B_intention_bit {     // in: words [n][4], r
+    PROBE_F(Const) {
+        uint32_t w[4];
+        for (int q = 0; q < 4; q++) w[q] = in<uint32_t>(a, 0)[4 * i + q];
+        out<int32_t>(a, 0)[i] = intention_bit(w, in<int>(a, 1)[i]);
+    }
+};
+struct B_replay_half_bits { PROBE_F(Const) { out<int>(a, 0)[i] = replay_half_bits(in<uint32_t>(a, 0)[i]); } };
+struct B_replay_feistel {    // in: seed, d, h (1 .. 16), x
+    PROBE_F(Const) {
+        const int h = in<int>(a, 2)[i];
+        out<uint32_t>(a, 0)[i] = (h >= 1 && h <= 16) ? replay_feistel(in<uint64_t>(a, 0)[i], in<uint64_t>(a, 1)[i], h, in<uint32_t>(a, 3)[i]) : ~0u;
+    }
+};
+struct B_replay_perm {       // in: seed, d, N (1 .. 2^31 - 1), j (< N)
+    PROBE_F(Const) {
+        const uint32_t N = in<uint32_t>(a, 2)[i], j = in<uint32_t>(a, 3)[i];
+        out<uint32_t>(a, 0)[i] = (N <= 0x7FFFFFFFu && j < N) ? replay_perm(in<uint64_t>(a, 0)[i], in<uint64_t>(a, 1)[i], N, j) : ~0u;
+    }
+};
+struct B_replay_append_plan {        // in: written, has_total (int), total, n_max, capacity (>= 1) -> out: (n, skip, start) [n][3]
+    PROBE_F(Const) {
+        const i64 capacity = in<i64>(a, 4)[i];
+        ReplayPlan P = {-1, -1, -1};
+        if (capacity >= 1) P = replay_append_plan(in<i64>(a, 0)[i], in<int>(a, 1)[i] != 0, in<i64>(a, 2)[i], in<i64>(a, 3)[i], capacity);
+        out<i64>(a, 0)[3 * i] = P.n; out<i64>(a, 0)[3 * i + 1] = P.skip; out<i64>(a, 0)[3 * i + 2] = P.start;
+    }
+};
+struct B_replay_append_slot {        // in: the plan's start, capacity, q
+    PROBE_F(Const) {
+        ReplayPlan P = {0, 0, in<i64>(a, 0)[i]};
+        out<i64>(a, 0)[i] = replay_append_slot(P, in<i64>(a, 1)[i], in<i64>(a, 2)[i]);
+    }
+};
+struct B_prio_key { PROBE_F(Const) { out<uint32_t>(a, 0)[i] = prio_key(in<int>(a, 0)[i] != 0, in<uint32_t>(a, 1)[i]); } };
+struct B_prio_partition {    // in: part_from [32] (one table per call), L
+    PROBE_F(Const) { const i64 *part_from = in<i64>(a, 0); out<int>(a, 0)[i] = prio_partition(part_from, in<i64>(a, 1)[i]); }
+};
+struct B_prio_draw_rank {    // in: ends [k[1]][k[0] + 1], seed, d, L; element i: row i / k[0], stratum i % k[0]
+    PROBE_F(Const) {
+        const i64 bsz = a.k[0];
+        out<int32_t>(a, 0)[i] = prio_draw_rank(in<int32_t>(a, 0) + (i / bsz) * (bsz + 1), in<uint64_t>(a, 1)[i], in<uint64_t>(a, 2)[i], (uint32_t)(i % bsz), in<i64>(a, 3)[i]);
+    }
+};
+struct B_prio_weight { PROBE_F(Const) { out<float>(a, 0)[i] = prio_weight(in<int32_t>(a, 0)[i], in<int32_t>(a, 1)[i], in<float>(a, 2)[i]); } };
+struct B_prio_update_bits { PROBE_F(Const) { out<uint32_t>(a, 0)[i] = prio_update_bits(in<float>(a, 0)[i], in<int>(a, 1)[i] != 0, in<float>(a, 2)[i]); } };
+struct B_prio_update_slot { PROBE_F(Const) { out<i64>(a, 0)[i] = prio_update_slot(in<i64>(a, 0)[i], in<i64>(a, 1)[i], in<i64>(a, 2)[i]); } };
+
+PROBE_EXPORT(philox4x32_10, 2, 1)
+PROBE_EXPORT(noise_gauss, 2, 1)
+PROBE_EXPORT(action_noise_z, 4, 1)
+PROBE_EXPORT(action_with_noise, 6, 1)
+PROBE_EXPORT(arrival_exp, 1, 1)
+PROBE_EXPORT(arrival_gap, 3, 1)
+PROBE_EXPORT(arrival_words, 5, 1)
+PROBE_EXPORT(intention_words, 5, 1)
+PROBE_EXPORT(intention_bit, 2, 1)
+PROBE_EXPORT(replay_half_bits, 1, 1)
+PROBE_EXPORT(replay_feistel, 4, 1)
+PROBE_EXPORT(replay_perm, 4, 1)
+PROBE_EXPORT(replay_append_plan, 5, 1)
+PROBE_EXPORT(replay_append_slot, 3, 1)
+PROBE_EXPORT(prio_key, 2, 1)
+PROBE_EXPORT(prio_partition, 2, 1)
+PROBE_EXPORT(prio_weight, 3, 1)
+PROBE_EXPORT(prio_update_bits, 3, 1)
+PROBE_EXPORT(prio_update_slot, 3, 1)
+
+// k[0] = bsz (strata per row, >= 1), k[1] = rows of the table; n <= rows * bsz
+extern "C" int pve_probe_prio_draw_rank(const pve_config *cfg, const pve_probe_args *a)
+{
+    const int bad = check(cfg, a, 4, 1);
+    if (bad) return bad;
+    if (a->k[0] < 1 || a->k[1] < 1 || a->n > (long long)a->k[0] * a->k[1]) return PROBE_E_ARGS;
+    return run<Const, B_prio_draw_rank>(make_const(*cfg), *a);
 }
 
 extern "C" int pve_probe_is_device(void) { return PVE_DEVICE_CODE; }
